@@ -6,7 +6,7 @@ synthetic BASELINE config-1 window (50 optimisable KF + 1 fixed, 20k landmarks, 
 observations, 4 asynchronous cameras, fp64), with the early-stop rule disabled so the iteration
 count is fixed.  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,6 +19,11 @@ estimates with one all_gather over RCCL (xGMI).  value = iterations of all ranks
 processes itself (torch.distributed.run as a child process, before anything touches the GPU) and
 exits with its status; rank 0's line is the job's line.  Under a launcher, WORLD_SIZE must equal
 --gpus.  --dry-launch prints the launch (command and rank environment) and exits.
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the result line.
+--full adds, each from a run of its own after the timed one: the per-kernel launch averages and the rooflines, the
+collectives, the phase breakdown and lba_set_problem, the LocalGPBA map calls and the CPU baselines (the last two
+unless --no-cpu).
 """
 import argparse
 import ctypes
@@ -325,6 +330,30 @@ def localgpba_map_calls(device, passes=3, seed=7):
     return out
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, prob, st, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy files: the
+    keyframes' poses and velocities and the landmarks (lba_get_state), the cameras' extrinsic estimates
+    (lba_get_cams) and the last lba_optimize's chi2 and lambda.  An array that would take the total past DUMP_BYTES
+    is cut to a fixed, seeded sample of its rows (in index order).  With several ranks every rank writes its own
+    problem's, the names prefixed rank<r>_."""
+    kfs, lm = prob.state()
+    cams = prob.cams()
+    out = {"kf_q": kfs["q"], "kf_t": kfs["t"], "kf_vel": kfs["vel"], "cam_q": cams["q"], "cam_t": cams["t"],
+           "chi2": np.array([st.chi2_initial, st.chi2_final, st.lambda_final]), "lm": lm}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES // world
+    for name, a in out.items():   # (the landmarks, the one large array, last: they get what the rest leaves)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > left:
+            rows = left // max(a[0].nbytes, 1)
+            a = a[np.sort(np.random.default_rng(20250912).choice(len(a), size=rows, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
+
+
 def main():
     if os.environ.get("_BENCH_OMP_CHILD"):   # cpu_baseline_omp's child: the oracle alone, one JSON line
         ap = argparse.ArgumentParser()
@@ -358,6 +387,13 @@ def main():
                     help="with --gpus N > 1 and no launcher: print the rank launch and exit (no GPU)")
     ap.add_argument("--f32-residual", action="store_true",
                     help="BASELINE configs[4]'s fp32 residuals + fp64 accumulate (LBA_FLAG_F32_RESIDUAL; default fp64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures, each in a run of its "
+                         "own: the per-kernel launch averages and rooflines, the collectives, the phase breakdown and "
+                         "lba_set_problem, the LocalGPBA map calls and the CPU baselines (the last two unless --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (lba_get_state, lba_get_cams and the last lba_optimize's "
+                         "chi2 / lambda) as DIR/<name>.npy (float64), before any further run touches the problem")
     args = ap.parse_args()
     if args.warmup is None:   # (from the name: nothing may load the library before launch_ranks)
         args.warmup = 100 if args.config == "cfg1_local_50kf" else (2 if "global" in args.config else 5)
@@ -457,6 +493,8 @@ def main():
     while done < args.steps:
         it = min(args.window_iters, args.steps - done)
         n, st = prob.optimize(it)
+        if n != it:   # (early stop is off: every call runs its iterations, so --steps is the timed count)
+            raise RuntimeError(f"lba_optimize({it}) ran {n} iterations")
         done += n
         ms_k += st.ms_k_linearize
         n_k += st.n_k_linearize
@@ -474,6 +512,49 @@ def main():
         tt = torch.tensor([dt], device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+
+    if args.dump_outputs:   # (first: the runs below continue from, or replace, the timed run's problem)
+        dump_outputs(args.dump_outputs, prob, st, rank, world)
+
+    # the result line of a plain run; --full adds its own measurements to it below
+    total_iters = done if gba else done * world   # farm: every rank its own window (weak); global BA: one problem
+    W = full if gba else win
+    value = total_iters / dt
+    live_k_ms, live_s_ms = ms_k / max(n_k, 1), ms_s / max(n_s, 1)
+    core = {
+        "metric": metric_for(args.config, W),
+        "value": value,
+        "unit": "LM iterations/s",
+        "n_gpus": world,
+        "steps": done,
+        "warmup": args.warmup,
+        "ms_per_step": dt * 1e3 / max(done, 1),
+        "higher_is_better": True,
+        "scaling": "strong" if gba else "weak",
+        "vs_baseline": None,
+        "dtype": "f32 residuals + f64 accumulate" if args.f32_residual else "f64",
+        "data": "synthetic (deterministic generator, amc_lba/synth.py, seed %d)" % args.seed,
+        "config": {"workload": f"{args.config}: {win.name or args.config} synthetic window",
+                   "n_kf": int(len(W.kfs)), "n_opt_kf": int((W.kfs["fixed"] == 0).sum()),
+                   "n_lm": int(len(W.lm)), "n_obs": int(len(W.obs)),
+                   "n_pairs": int(W.n_pairs) if rank == 0 else None,   # (a pass over the observations: rank 0 prints)
+                   "n_cam": int(len(W.cams)), "window_iters": args.window_iters, "solve": args.solve,
+                   "parallelism": ((f"distributed factorisation x{world} (subtree per rank, RCCL all-reduce of the "
+                                    "top per trial)" if args.gba_solve == "split" else
+                                    f"landmark partition x{world} (RCCL all-reduce per trial)") if gba else
+                                   f"window farm x{world}") if world > 1 else "single window",
+                   "window_build_and_setup_s": t_setup},   # (the synthetic window generation in Python + lba_set_problem)
+        "live_sampled_ms": {"k_lin_schur": live_k_ms, "k_chol_flow": live_s_ms,
+                            "note": "the timed run's own sampled dispatch events (one trial in ten)"},
+        "trials_per_step": trials / max(done, 1),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(core), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # per-kernel launch durations for the rooflines: the timed run carries events on one trial in ten only (they idle
     # the device ~5 us each); a further, untimed optimize with events on every trial's k_lin_schur and k_chol_flow
@@ -570,12 +651,7 @@ def main():
         set_problem_phases = ({k: float(np.median([d[k] for d in sp_ph])) for k in sp_ph[0]} if sp_ph else None)
         ph.close()
     if rank == 0:
-        # window farm: every rank runs its own window (weak scaling); global BA: one problem (strong)
-        total_iters = done if gba else done * world
-        W = full if gba else win
-        value = total_iters / dt
         # launch averages from the dedicated run (the timed run's sampled events are reported beside them)
-        live_k_ms, live_s_ms = ms_k / max(n_k, 1), ms_s / max(n_s, 1)
         if mk_n:
             ms_k, n_k = mk_ms, mk_n
         if ms_n:
@@ -609,29 +685,9 @@ def main():
         chol_pmc, chol_pmc_src = pmc_summary(args.config, "k_chol_flow")
         achieved = B / (k_ms * 1e-3) / 1e9 if n_k else None
         achieved_f = F / (k_ms * 1e-3) / 1e12 if n_k else None
-        workload = f"{args.config}: {win.name or args.config} synthetic window"
         traffic, traffic_src = pmc_traffic(args.config)
         line = {
-            "metric": metric_for(args.config, W),
-            "value": value,
-            "unit": "LM iterations/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt * 1e3 / done,
-            "higher_is_better": True,
-            "scaling": "strong" if gba else "weak",
-            "vs_baseline": None,
-            "dtype": "f32 residuals + f64 accumulate" if args.f32_residual else "f64",
-            "data": "synthetic (deterministic generator, amc_lba/synth.py, seed %d)" % args.seed,
-            "config": {"workload": workload, "n_kf": int(len(W.kfs)), "n_opt_kf": int((W.kfs["fixed"] == 0).sum()),
-                       "n_lm": int(len(W.lm)), "n_obs": int(len(W.obs)), "n_pairs": int(W.n_pairs),
-                       "n_cam": int(len(W.cams)), "window_iters": args.window_iters, "solve": args.solve,
-                       "parallelism": ((f"distributed factorisation x{world} (subtree per rank, RCCL all-reduce of the "
-                                        "top per trial)" if args.gba_solve == "split" else
-                                        f"landmark partition x{world} (RCCL all-reduce per trial)") if gba else
-                                       f"window farm x{world}") if world > 1 else "single window",
-                       "window_build_and_setup_s": t_setup},   # (the synthetic window generation in Python + lba_set_problem)
+            **core,
             # the sweep's algorithmic intensity (F / B ~ 44 FLOP/B at config 1) is above the fp64 ridge point
             # (78.6 TF / 8 TB/s ~ 10 FLOP/B): its roofline is fp64 compute; the HBM view is kept beside it
             "roofline": {"bound": "mfma", "kernel": "k_lin_schur", "achieved": achieved_f,
@@ -661,9 +717,6 @@ def main():
                                "frac_structural": (F_solve / (s_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS) if n_s else None,
                                "note": solve_note,
                                "solver": sinfo, "flops_factor": F_fac, "flops_substitution": F_sub},
-            "live_sampled_ms": {"k_lin_schur": live_k_ms, "k_chol_flow": live_s_ms,
-                                "note": "the timed run's own sampled dispatch events (one trial in ten)"},
-            "trials_per_step": trials / max(done, 1),
             "phases_ms_per_step": phase,
         }
         # the contract's `roofline` is the DOMINANT kernel's (the longer average launch); the sweep's stays beside it

@@ -8,9 +8,10 @@ T=$1
 for c in ${CFGS:-cfg1_local_50kf}; do
   for v in head new head2 new2; do
     case $v in head*) export AMC_LBA_LIB=$PWD/amc-slam_amd/lib/exp/head.so;; *) unset AMC_LBA_LIB;; esac
-    timeout -k 10 300 python bench.py --config $c --steps ${STEPS:-200} --warmup 10 --no-cpu > gpurun_out/${T}_${c}_$v.bench.log 2>&1
+    LOG=${OUT_DIR:-bench_out}/${T}_${c}_$v.bench.log; mkdir -p "$(dirname "$LOG")"
+    timeout -k 10 300 python bench.py --config $c --steps ${STEPS:-200} --warmup 10 --full --no-cpu > "$LOG" 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "$v rc=$rc"; exit $rc; }
-    python - gpurun_out/${T}_${c}_$v.bench.log $v <<'PY'
+    python - "$LOG" $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
     if l.startswith('{'):

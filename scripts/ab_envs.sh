@@ -9,9 +9,10 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for kv in "$@"; do
     i=$((i + 1))
     if [ -n "$kv" ]; then E="env $kv"; else E=""; fi
-    $E timeout -k 10 300 python bench.py --config ${CFG:-cfg1_local_50kf} --steps ${STEPS:-200} --warmup 10 --no-cpu > gpurun_out/${T}_${i}_$r.bench.log 2>&1
+    LOG=${OUT_DIR:-bench_out}/${T}_${i}_$r.bench.log; mkdir -p "$(dirname "$LOG")"
+    $E timeout -k 10 300 python bench.py --config ${CFG:-cfg1_local_50kf} --steps ${STEPS:-200} --warmup 10 --full --no-cpu > "$LOG" 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "$kv rc=$rc"; exit $rc; }
-    python - gpurun_out/${T}_${i}_$r.bench.log "${kv:-base}" <<'PY'
+    python - "$LOG" "${kv:-base}" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
     if l.startswith('{'):

@@ -22,7 +22,7 @@ for c in $CONFIGS; do
   for r in $(seq 1 "${ROUNDS:-2}"); do
     for v in $VARIANTS; do
       echo -n "$c $v: " >> "$OUT"
-      AMC_LBA_LIB=$E/$v.so timeout -k 10 300 python bench.py --config "$c" --steps "$ST" --warmup "$W" --no-cpu 2>/dev/null \
+      AMC_LBA_LIB=$E/$v.so timeout -k 10 300 python bench.py --config "$c" --steps "$ST" --warmup "$W" --full --no-cpu 2>/dev/null \
         | grep "^{" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],2), 'ms/step', round(d['ms_per_step']*1e3,2), 'solve us', round(d['roofline_solve']['avg_launch_ms']*1e3,1), 'sweep us', round(d['roofline_sweep']['avg_launch_ms']*1e3,1), 'trials', d['trials_per_step'])" >> "$OUT" || exit 1
     done
   done

@@ -9,9 +9,10 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for c in ${CFGS:-cfg1_local_50kf}; do
     for v in "$@"; do
       if [ "$v" = tree ]; then unset AMC_LBA_LIB; else export AMC_LBA_LIB=$PWD/amc-slam_amd/lib/exp/$v.so; fi
-      timeout -k 10 300 python bench.py --config $c --steps ${STEPS:-200} --warmup 10 --no-cpu > gpurun_out/${T}_${c}_${v}_$r.bench.log 2>&1
+      LOG=${OUT_DIR:-bench_out}/${T}_${c}_${v}_$r.bench.log; mkdir -p "$(dirname "$LOG")"
+      timeout -k 10 300 python bench.py --config $c --steps ${STEPS:-200} --warmup 10 --full --no-cpu > "$LOG" 2>&1
       rc=$?; [ $rc -eq 0 ] || { echo "$v rc=$rc"; exit $rc; }
-      python - gpurun_out/${T}_${c}_${v}_$r.bench.log $v <<'PY'
+      python - "$LOG" $v <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
     if l.startswith('{'):

@@ -7,6 +7,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out
 T=$1; shift
+O=${OUT_DIR:-bench_out}; mkdir -p $O   # (the bench / drv steps' logs)
 python - <<'PY' || exit 3
 import sys; sys.path.insert(0, 'amc-slam_amd')
 import build
@@ -16,9 +17,9 @@ PY
 for s in "$@"; do
   case $s in
     list) (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 -L > $OLDPWD/gpurun_out/${T}_counters.txt 2>&1); rc=$? ;;
-    bench) timeout -k 10 300 python bench.py --steps ${STEPS:-200} --warmup 10 --no-cpu > gpurun_out/${T}_bench.log 2>&1; rc=$?
-           grep '^{' gpurun_out/${T}_bench.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('value', round(d['value'],1), 'ms', round(d['ms_per_step']*1e3,2), 'sweep', round(d.get('roofline_sweep', d['roofline'])['avg_launch_ms']*1e3,2), 'solve', round(d['roofline_solve']['avg_launch_ms']*1e3,2))" ;;
-    drv) timeout -k 10 600 python bench.py > gpurun_out/${T}_drv.log 2>&1; rc=$?; tail -c 600 gpurun_out/${T}_drv.log ;;
+    bench) timeout -k 10 300 python bench.py --steps ${STEPS:-200} --warmup 10 --full --no-cpu > $O/${T}_bench.log 2>&1; rc=$?
+           grep '^{' $O/${T}_bench.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('value', round(d['value'],1), 'ms', round(d['ms_per_step']*1e3,2), 'sweep', round(d.get('roofline_sweep', d['roofline'])['avg_launch_ms']*1e3,2), 'solve', round(d['roofline_solve']['avg_launch_ms']*1e3,2))" ;;
+    drv) timeout -k 10 600 python bench.py --full > $O/${T}_drv.log 2>&1; rc=$?; tail -c 600 $O/${T}_drv.log ;;
     tests) timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q -rf --durations=15 --timeout 300 --timeout-method thread > gpurun_out/${T}_pytest.log 2>&1; rc=$?; tail -3 gpurun_out/${T}_pytest.log ;;
     quick) timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu ${TESTS:-tests/test_gpu_parity.py} > gpurun_out/${T}_quick.log 2>&1; rc=$?; tail -3 gpurun_out/${T}_quick.log ;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/gpurun_out/prof_$T -o run -- python3 $OLDPWD/bench.py --steps 25 --warmup 3 --no-cpu > $OLDPWD/gpurun_out/${T}_prof.log 2>&1); rc=$?
