@@ -179,7 +179,14 @@ int lba_set_config(lba_problem* p, const lba_config* cfg);
 
 /* Copy a window to the device (replaces SparseOptimizer::addVertex/addEdge +
  * initializeOptimization, sparse_optimizer.cpp:197-267).  vel_kfs lists the KFs carrying an
- * EdgeVelocity (info QcInv(2,2), Optimizer.cc:858-870). */
+ * EdgeVelocity (info QcInv(2,2), Optimizer.cc:858-870).  The arrays may come in any order: fixed
+ * keyframes anywhere, kf_a any other keyframe of the window (not only the array neighbour), edges on
+ * fixed keyframes (an edge whose vertices are all fixed is inactive).  A vertex no active edge touches
+ * (a landmark without an observation, a free keyframe without an edge) is inactive like in g2o: it has
+ * no rows in H / b / dx, which are compressed to the active vertices in array order, and its state is
+ * never changed.  Keyframe quaternions are normalised on the way in like the Sophus cast (as in
+ * lba_set_state), so lba_get_state returns a fixed or inactive keyframe's t and vel bit for bit as
+ * passed and its q normalised; an inactive landmark comes back bit for bit. */
 int lba_set_problem(lba_problem* p,
                     const lba_kf* kfs, int32_t n_kf,
                     const double* lm_xyz, int32_t n_lm,

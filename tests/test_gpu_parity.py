@@ -13,7 +13,7 @@ import pytest
 
 import orc
 from amc_lba import LbaError, Problem
-from amc_lba.abi import LBA_E_EMPTY, LBA_E_LIMIT, MONO_GP, STEREO_GP, PRIOR_DTYPE
+from amc_lba.abi import LBA_E_EMPTY, LBA_E_LIMIT, PRIOR_DTYPE
 from amc_lba.synth import make_config_window, make_window
 
 pytestmark = pytest.mark.gpu
