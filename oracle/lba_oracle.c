@@ -1803,6 +1803,22 @@ static void trk_build(trk_t* T, double* H, double* b) {
     }
 }
 
+/* Conditioning of a tracking input (for the tests that compare `iterations` with another implementation):
+ * the LM iterations since the last orc_track_floor_iterations(1) in which a trial's gain
+ * |currentChi - tempChi| was below TRK_FLOOR * currentChi, i.e. within a few hundred times the rounding
+ * error of the sum itself (N eps, N some hundred edges), at a point where accepting or rejecting that trial
+ * changes the iteration count.  It does not when the round ends with this iteration whatever the trial
+ * gives: two bad iterations before it (accepted: the third; rejected max_trials times or rho == 0: stop),
+ * the tenth iteration, or early_stop off.  An input that counts one has its `iterations` decided by
+ * rounding, in g2o as much as here. */
+#define TRK_FLOOR 1e-11
+static int trk_floor_iterations = 0;
+int orc_track_floor_iterations(int reset) {
+    int n = trk_floor_iterations;
+    if (reset) trk_floor_iterations = 0;
+    return n;
+}
+
 static int trk_lm_iteration(trk_t* T, int iteration, double* lambda, double* ni, int* nbad, int* trials) {
     orc_problem* p = T->p;
     const int d0 = trk_dof0(T), n = 24 - d0;
@@ -1817,7 +1833,7 @@ static int trk_lm_iteration(trk_t* T, int iteration, double* lambda, double* ni,
         *nbad = 0;
     }
     double rho = 0.0;
-    int qmax = 0;
+    int qmax = 0, at_floor = 0;
     kf_t bak[2];
     do {
         memcpy(bak, p->kf, sizeof(bak));
@@ -1835,6 +1851,8 @@ static int trk_lm_iteration(trk_t* T, int iteration, double* lambda, double* ni,
             }
         }
         tempChi = trk_errors(T);
+        if (ok2 && fabs(currentChi - tempChi) < TRK_FLOOR * fabs(currentChi) && *nbad < 2 && iteration < 9 && p->cfg.early_stop)
+            at_floor = 1;
         if (!ok2) tempChi = DBL_MAX;
         rho = currentChi - tempChi;
         double scale = 1e-3;
@@ -1854,6 +1872,7 @@ static int trk_lm_iteration(trk_t* T, int iteration, double* lambda, double* ni,
         }
         qmax++;
     } while (rho < 0 && qmax < p->cfg.max_trials);
+    trk_floor_iterations += at_floor;
     *trials += qmax;
     if (qmax == p->cfg.max_trials || rho == 0) return LBA_RESULT_TERMINATE;
     if ((iniChi - currentChi) * 1e3 < iniChi) (*nbad)++;

@@ -56,6 +56,9 @@ int    orc_prior_linearize(orc_problem* p, int prior_index, double* err, double*
  * fr->cur, tob[].outlier, fr->n_good (returned), fr->iterations */
 int    orc_track_pose(const lba_config* cfg, lba_track_frame* fr, lba_track_obs* tob, int n,
                       const lba_cam* cams, int n_cam);
+/* LM iterations of the orc_track_pose calls since the last reset whose accept / reject decision lay within
+ * rounding of the chi2 sum and changes `iterations` (the conditioning of a test input; lba_oracle.c) */
+int    orc_track_floor_iterations(int reset);
 
 /* Lie / GP primitives for golden-vector tests */
 void   orc_se3_exp(const double xi[6], double q[4], double t[3]);

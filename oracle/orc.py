@@ -285,3 +285,8 @@ def track_pose(cfg, frame, obs, cams):
     L.orc_track_pose.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p, ctypes.c_int]
     return L.orc_track_pose(ctypes.byref(cfg), ptr(frame), ptr(obs), len(obs), ptr(cams), len(cams))
 
+
+def track_floor_iterations(reset=True):
+    """orc_track_floor_iterations: LM iterations of the track_pose calls since the last reset whose accept /
+    reject decision was taken within rounding of the chi2 sum and changes the iteration count."""
+    return lib().orc_track_floor_iterations(int(reset))
