@@ -107,6 +107,8 @@ def lib():
         L.lba_setup_host_profile.argtypes = [ctypes.POINTER(LbaConfig), vp, ctypes.c_int32, vp, ctypes.c_int32, vp,
                                              ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32,
                                              _dp, _ip]
+        if hasattr(L, "lba_setup_tile_shapes"):   # (absent from builds before it: A/B runs of older libraries)
+            L.lba_setup_tile_shapes.argtypes = L.lba_setup_host_profile.argtypes[:-2] + [_ip]
         L.lba_farm_match.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _lp, _lp, _ip, ctypes.c_int32, _ip]
         if hasattr(L, "lba_partition_assign"):   # (absent from builds before it: A/B runs of older libraries)
             L.lba_partition_assign.argtypes = [ctypes.POINTER(LbaConfig), vp, ctypes.c_int32, ctypes.c_int32, vp,
@@ -124,7 +126,7 @@ def exported_symbols():
             "lba_pose_dim", "lba_set_partition", "lba_rccl_unique_id", "lba_set_partition_rccl", "lba_group_create",
             "lba_group_destroy", "lba_set_partition_group", "lba_get_cams", "lba_set_farm", "lba_set_farm_rccl",
             "lba_set_farm_group", "lba_farm_plan", "lba_farm_exchange", "lba_farm_match", "lba_solver_info", "lba_solver_flops", "lba_device_bytes", "lba_setup_phases",
-            "lba_kernel_modes", "lba_setup_host_profile", "lba_debug_pool_stress", "lba_debug_lie", "lba_partition_assign", "lba_kf_owner", "lba_split_info"]
+            "lba_kernel_modes", "lba_setup_host_profile", "lba_setup_tile_shapes", "lba_debug_pool_stress", "lba_debug_lie", "lba_partition_assign", "lba_kf_owner", "lba_split_info"]
 
 
 def setup_host_profile(win, **cfg_over):
@@ -147,6 +149,33 @@ def setup_host_profile(win, **cfg_over):
     if rc != 0:
         raise LbaError(rc, "lba_setup_host_profile failed")
     return ms, cnt
+
+
+TILE_SHAPE_FIELDS = ("tiles", "obs", "rows", "samples", "sample_rows", "landmarks", "pairs", "kfs", "schur_entries",
+                     "seg_tiles", "seg_obs", "seg_rows", "seg_samples", "seg_pairs")
+
+
+def setup_tile_shapes(win, **cfg_over):
+    """lba_setup_tile_shapes: the largest tile shapes of lba_set_problem's host preprocessing (no GPU), as a dict:
+    over the regular tiles their number `tiles` and the maxima of a tile's obs, rows, samples, sample_rows (rows of
+    one pose sample), landmarks, pairs, kfs, schur_entries; over the segment tiles of heavy landmarks seg_tiles and
+    the maxima seg_obs, seg_rows, seg_samples, seg_pairs."""
+    kw = dict(win.cfg)
+    kw.update(cfg_over)
+    cfg = make_config(**kw)
+    kfs = np.ascontiguousarray(win.kfs, dtype=KF_DTYPE)
+    lm = np.ascontiguousarray(win.lm, dtype=np.float64)
+    obs = np.ascontiguousarray(win.obs, dtype=OBS_DTYPE)
+    pri = np.ascontiguousarray(win.priors, dtype=PRIOR_DTYPE)
+    vel = np.ascontiguousarray(win.vel_kfs, dtype=np.int32)
+    cams = np.ascontiguousarray(win.cams, dtype=CAM_DTYPE)
+    sh = np.zeros(len(TILE_SHAPE_FIELDS), dtype=np.int32)
+    rc = lib().lba_setup_tile_shapes(ctypes.byref(cfg), ptr(kfs), len(kfs), ptr(lm), len(lm), ptr(obs), len(obs),
+                                     ptr(pri), len(pri), ptr(vel), len(vel), ptr(cams), len(cams),
+                                     sh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    if rc != 0:
+        raise LbaError(rc, "lba_setup_tile_shapes failed")
+    return dict(zip(TILE_SHAPE_FIELDS, (int(v) for v in sh)))
 
 
 def debug_lie(xi, q=None, t=None, device=0):

@@ -78,6 +78,7 @@ struct lba_problem {
     bool host_only = false;       // lba_setup_host_profile: stop set_problem after the host preprocessing
     uint32_t setup_hash = 0;      // (host_only) fingerprint of the tiling / slab layout
     int setup_tiles = 0;
+    int32_t setup_shapes[LBA_TILE_SHAPES] = {};   // (host_only) lba_setup_tile_shapes
     std::vector<double> setup_ms; // wall time of the set-up phases (order/pairs, tiles, slots/state, ...)
     PlanCache plan_cache;
     // device buffers of the window, in set_problem's allocation order; the next set_problem reuses
@@ -1547,6 +1548,29 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
         mix(t_kf0); mix(t_nkf); mix(tkf_list); mix(sent_k1); mix(sent_k2); mix(pair_r0); mix(lm_r0);
         p->setup_hash = h;
         p->setup_tiles = n_tiles;
+        // the largest tile shapes (lba_setup_tile_shapes): regular tiles in [0..8], segment tiles in [9..13]
+        int32_t* sh = p->setup_shapes;
+        std::fill(sh, sh + LBA_TILE_SHAPES, 0);
+        auto up = [](int32_t& m, int v) { m = std::max<int32_t>(m, v); };
+        for (int t = 0; t < n_tiles; ++t) {
+            const bool reg = t < n_stiles;
+            const int rows = lm_r0[t_lm0[t] + t_nlm[t]] - lm_r0[t_lm0[t]];
+            int srows = 0;
+            for (int s = t_smp0[t]; s < t_smp0[t] + t_nsmp[t]; ++s) srows = std::max(srows, tsm_rows[s] >> 16);
+            ++sh[reg ? 0 : 9];
+            up(sh[reg ? 1 : 10], t_nobs[t]);
+            up(sh[reg ? 2 : 11], rows);
+            up(sh[reg ? 3 : 12], t_nsmp[t]);
+            if (reg) {
+                up(sh[4], srows);
+                up(sh[5], t_nlm[t]);
+                up(sh[6], t_npair[t]);
+                up(sh[7], t_nkf[t]);
+                up(sh[8], t_nsent[t]);
+            } else {
+                up(sh[13], t_npair[t]);
+            }
+        }
         return LBA_OK;
     }
     // ---- device upload
@@ -2872,6 +2896,26 @@ int lba_setup_host_profile(const lba_config* cfg, const lba_kf* kfs, int32_t n_k
         counts[3] = p.setup_tiles;
         counts[4] = (int32_t)p.setup_hash;
     }
+    return LBA_OK;
+}
+
+int lba_setup_tile_shapes(const lba_config* cfg, const lba_kf* kfs, int32_t n_kf, const double* lm_xyz, int32_t n_lm,
+                          const lba_obs* obs, int32_t n_obs, const lba_prior* priors, int32_t n_priors,
+                          const int32_t* vel_kfs, int32_t n_vel, const lba_cam* cams, int32_t n_cam,
+                          int32_t shapes[LBA_TILE_SHAPES]) {
+    if (!cfg || !shapes) return LBA_E_ARG;
+    lba_problem p;   // (as lba_setup_host_profile: no device)
+    p.cfg = *cfg;
+    p.host_only = true;
+    try {
+        const int rc = set_problem(&p, kfs, n_kf, lm_xyz, n_lm, obs, n_obs, priors, n_priors, vel_kfs, n_vel, cams, n_cam);
+        if (rc < 0) return rc;
+    } catch (const ApiError& e) {
+        return e.code;
+    } catch (const HipError&) {
+        return LBA_E_HIP;
+    }
+    std::copy(p.setup_shapes, p.setup_shapes + LBA_TILE_SHAPES, shapes);
     return LBA_OK;
 }
 

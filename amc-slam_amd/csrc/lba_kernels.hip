@@ -152,6 +152,15 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// v of the neighbouring lane (lane ^ 1; both lanes active)
+__device__ __forceinline__ double lane_swap1(double v) {
+    const unsigned long long u = __double_as_longlong(v);
+    constexpr int QP_1032 = 0xB1;   // DPP quad_perm [1, 0, 3, 2]
+    const unsigned lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, QP_1032, 0xf, 0xf, true);
+    const unsigned hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), QP_1032, 0xf, 0xf, true);
+    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+
 // deterministic block sum (blockDim multiple of 64, <= 1024); valid in thread 0
 template <int NT>
 __device__ __forceinline__ double block_sum(double v, double* red) {
@@ -454,38 +463,37 @@ __global__ __launch_bounds__(PREP_THREADS) void k_gp_prep(DevProblem P, int sel,
     if (k < P.n_kf) kf_pose_record(P, gps, k, kst + (size_t)k * KF_STRIDE);
 }
 
-// One (tile sample, 9-output chunk) task: outputs 9 CH .. 9 CH + 8 of the sample's partial, i.e. the
-// upper triangle of M = sum_rows s J1^T J1 (outputs 0..20, row-major) and g = sum_rows s J1^T e
-// (21..26), over the sample's contiguous rows.
-template <int CH>
+// One (tile sample, output group) task: outputs G grp .. G grp + G - 1 of the sample's partial, i.e. of the upper
+// triangle of M = sum_rows s J1^T J1 (outputs 0..20, row-major) and of g = sum_rows s J1^T e (21..26), over the
+// sample's contiguous rows.  Every output has its own accumulation acc = fma(s x, y, acc) in row order, x / y the
+// output's two columns of the row [J1 e] (per-lane column offsets: no lane runs another lane's outputs).
+template <int G>
 __device__ __forceinline__ void smp_task(const DevProblem& P, const double* rows, const double* rw, int r0, int nr,
-                                         int mslot) {
-    constexpr unsigned char ui[21] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5};
-    constexpr unsigned char uj[21] = {0, 1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 2, 3, 4, 5, 3, 4, 5, 4, 5, 5};
-    double acc[9];
+                                         int mslot, int grp) {
+    static_assert(SM_STRIDE % G == 0, "whole groups");
+    const double *X[G], *Y[G];
+    double acc[G];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) acc[q] = 0.0;
+    for (int k = 0; k < G; ++k) {
+        // the output's columns: M(i, j), i <= j, at 6 i - i (i - 1) / 2 + (j - i) -> (x, y) = (i, j); g(l) -> (l, 6)
+        const int out = G * grp + k;
+        const int i = (out >= 6) + (out >= 11) + (out >= 15) + (out >= 18) + (out >= 20);
+        X[k] = rows + r0 * ROW_STRIDE + (out < 21 ? i : out - 21);
+        Y[k] = rows + r0 * ROW_STRIDE + (out < 21 ? out - (6 * i - i * (i - 1) / 2) + i : 6);
+        acc[k] = 0.0;
+    }
+    const double* W = rw + r0;
     // (unrolled: the next rows' LDS reads are issued ahead of this row's FMAs; the same order of additions)
 #pragma unroll 4
-    for (int r = r0; r < r0 + nr; ++r) {
-        const double* R = rows + r * ROW_STRIDE;
-        const double sw = rw[r];
-        double j[7];
+    for (int r = 0; r < nr; ++r) {
+        const double sw = W[r];
 #pragma unroll
-        for (int c = 0; c < 7; ++c) j[c] = R[c];   // J1 (6), e
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-            constexpr int base = 9 * CH;
-            const int idx = base + q;
-            const double x = idx < 21 ? j[ui[idx < 21 ? idx : 0]] : j[idx - 21];
-            const double y = idx < 21 ? j[uj[idx < 21 ? idx : 0]] : j[6];
-            acc[q] += (sw * x) * y;
-        }
+        for (int k = 0; k < G; ++k) acc[k] = fma(sw * X[k][r * ROW_STRIDE], Y[k][r * ROW_STRIDE], acc[k]);
     }
     if (!LBA_INB(P, mslot, P.n_mslots, "mslab")) return;
-    double* m = P.mslab + (size_t)mslot * MS_PITCH + 9 * CH;
+    double* m = P.mslab + (size_t)mslot * MS_PITCH + G * grp;
 #pragma unroll
-    for (int q = 0; q < 9; ++q) m[q] = acc[q];
+    for (int k = 0; k < G; ++k) m[k] = acc[k];
 }
 
 template <int NT>
@@ -710,7 +718,7 @@ __device__ void edge_item(const DevProblem& P, int sel, int idx, const int tid, 
 // tile, so the tile's Hpl goes from the linearisation straight into the elimination in LDS (no second
 // launch reads it back):
 //   1. one observation per lane: residual, Huber weight, rows [J1 e Jp] -> LDS, robust chi2 partial
-//   2. per (tile sample, 9-output chunk): the sample's M / g partial -> mslab (J = J1 N, so
+//   2. per (tile sample, three of its 27 outputs): the sample's M / g partial -> mslab (J = J1 N, so
 //      sum J^T W J = N^T M N per sample, formed by k_expand)
 //   3. per (pair, 6-row half): Hpl(k, lm) = sum over its (observation, side) entries of N_side^T G,
 //      G = rho' w sum_rows J1^T Jp -> HBM (k_update's back-substitution) and registers
@@ -846,13 +854,13 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
     LBA_TMARKI(P.tdbg_lin, tile, 1);
 
     // ---- phase 2: the tile's partial of every pose sample it observes, in the sample's 6-dim space
-    for (int task = tid; task < nts * 3; task += LS_THREADS) {
-        const int ts = task / 3, ch = task - 3 * ts;
+    //      (three outputs per lane, a sample's nine lanes consecutive: its slot is stored as one run; the mean
+    //      tile's 24 samples fill one pass of the workgroup, where 9 outputs per lane left waves 2 and 3 idle)
+    constexpr int P2_G = 3, P2_NG = SM_STRIDE / P2_G;
+    for (int task = tid; task < nts * P2_NG; task += LS_THREADS) {
+        const int ts = task / P2_NG, grp = task - P2_NG * ts;
         const int meta = tsm[2 * ts], mslot = tsm[2 * ts + 1];
-        const int r0 = meta & 0xffff, nr = meta >> 16;
-        if (ch == 0) smp_task<0>(P, rows, rw, r0, nr, mslot);
-        else if (ch == 1) smp_task<1>(P, rows, rw, r0, nr, mslot);
-        else smp_task<2>(P, rows, rw, r0, nr, mslot);
+        smp_task<P2_G>(P, rows, rw, meta & 0xffff, meta >> 16, mslot, grp);
     }
     LBA_TMARKI(P.tdbg_lin, tile, 2);
 
@@ -866,6 +874,8 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
 #pragma unroll
             for (int q = 0; q < 9; ++q) H[q] = 0.0;
             b[0] = b[1] = b[2] = 0.0;
+            // (unrolled: the next rows' index and row reads are issued ahead of this row's FMAs, which keep their order)
+#pragma unroll 4
             for (int q = lr0[t]; q < lr0[t + 1]; ++q) {
                 const int r = lrow[q];
                 const double* Rr = rows + r * ROW_STRIDE;
@@ -991,7 +1001,54 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
     //      bank conflicts) and D_m^-1 is one broadcast read.  Every entry takes 8 consecutive lanes (a diagonal
     //      entry's rows 6..11 x columns 0..5 too, though never assembled), which store its slot line by line (spos_of)
     const int nkf = P.tile_nkf[tile];
-    for (int task = tid; task < nsent * 8; task += LS_THREADS) {
+    //      A last pass of at most LS_THREADS / 2 tasks (8 KFs' 36 entries leave one of 32) is split over lane pairs,
+    //      lane h of a pair taking columns 3 h .. 3 h + 2 of its task's six (each output: the same landmark order
+    //      and fma nest), so it costs about half a pass; the pair then swaps its blocks and lane h stores lines
+    //      5 h .. of the task's nine, each still written whole by one store of the task's 8 pairs.
+    const int ntask = nsent * 8;
+    const int nfull = ntask % LS_THREADS > LS_THREADS / 2 ? ntask : ntask - ntask % LS_THREADS;
+    if (nfull + (tid >> 1) < ntask) {
+        const int task = nfull + (tid >> 1), h = tid & 1;
+        const int q = task >> 3, rg = (task >> 1) & 3, ch = task & 1;
+        const short* p1 = pidx + (scode[q] & 255) * PIDX_STRIDE;
+        const short* p2 = pidx + (scode[q] >> 8) * PIDX_STRIDE;
+        double acc[9];
+#pragma unroll
+        for (int u = 0; u < 9; ++u) acc[u] = 0.0;
+        for (int m = 0; m < nlm; ++m) {
+            const double* A = U + p1[m] * 36 + rg * 9;             // rows 3 rg .. 3 rg + 2 of W(m, k1)
+            const double* B = U + p2[m] * 36 + ch * 18 + h * 9;    // rows 6 ch + 3 h .. + 2 of W(m, k2)
+            const double* dd = Dl + m * DL_STRIDE + 4;
+            double a[9], b[9];
+#pragma unroll
+            for (int u = 0; u < 9; ++u) a[u] = A[u] * dd[u % 3];
+#pragma unroll
+            for (int u = 0; u < 9; ++u) b[u] = B[u];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    acc[i * 3 + j] = fma(a[i * 3 + 2], b[j * 3 + 2],
+                                         fma(a[i * 3 + 1], b[j * 3 + 1], fma(a[i * 3], b[j * 3], acc[i * 3 + j])));
+        }
+        double c[18];   // the task's 3 x 6 block: own columns and the partner lane's
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double mine = acc[i * 3 + j], other = lane_swap1(mine);
+                c[i * 6 + j] = h ? other : mine;
+                c[i * 6 + 3 + j] = h ? mine : other;
+            }
+        if (LBA_INB(P, sslt[q], P.n_sslots, "sslab")) {
+            double* o = P.sslab + (size_t)sslt[q] * 144 + 2 * (task & 7) + (h ? 16 * 5 : 0);
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+                if (k < 4 || !h) st16(o + 16 * k, h ? c[2 * (k < 4 ? k + 5 : 0)] : c[2 * k],
+                                      h ? c[2 * (k < 4 ? k + 5 : 0) + 1] : c[2 * k + 1]);
+        }
+    }
+    for (int task = tid; task < nfull; task += LS_THREADS) {
         const int q = task >> 3, rg = (task >> 1) & 3, ch = task & 1;
         const short* p1 = pidx + (scode[q] & 255) * PIDX_STRIDE;
         const short* p2 = pidx + (scode[q] >> 8) * PIDX_STRIDE;
@@ -1024,7 +1081,8 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
     //      (block_solver.hpp:395-401); absent pairs read the zero pair
     {
         const int kf0 = P.tile_kf0[tile];
-        for (int task = tid; task < nkf * 12; task += LS_THREADS) {
+        // (tasks counted from the top lane: phase 6's last pass fills the lanes from the bottom)
+        for (int task = LS_THREADS - 1 - tid; task < nkf * 12; task += LS_THREADS) {
             const int l = task / 12, r = task - 12 * l;
             const short* pr = pidx + l * PIDX_STRIDE;
             double v0 = 0.0, v1 = 0.0;

@@ -313,6 +313,16 @@ int lba_setup_host_profile(const lba_config* cfg, const lba_kf* kfs, int32_t n_k
                            const lba_obs* obs, int32_t n_obs, const lba_prior* priors, int32_t n_priors,
                            const int32_t* vel_kfs, int32_t n_vel, const lba_cam* cams, int32_t n_cam,
                            double phase_ms[3], int32_t counts[5]);
+/* Diagnostics: the largest tile shapes of the same host preprocessing (no device): the work sizes of the sweep's
+ * per-tile phases.  shapes[0..8] over the regular (eliminating) tiles: their number, then the maxima of a tile's
+ * observations, Jacobian rows, pose samples, rows of one pose sample, landmarks, (KF, landmark) pairs, KFs and
+ * Schur entries; shapes[9..13] over the segment tiles of heavy landmarks: their number, then the maxima of
+ * observations, rows, pose samples and pairs.  Returns LBA_OK or the error lba_set_problem would return. */
+#define LBA_TILE_SHAPES 14
+int lba_setup_tile_shapes(const lba_config* cfg, const lba_kf* kfs, int32_t n_kf, const double* lm_xyz, int32_t n_lm,
+                          const lba_obs* obs, int32_t n_obs, const lba_prior* priors, int32_t n_priors,
+                          const int32_t* vel_kfs, int32_t n_vel, const lba_cam* cams, int32_t n_cam,
+                          int32_t shapes[LBA_TILE_SHAPES]);
 /* Diagnostics: `passes` back-to-back parallel passes of lba_set_problem's host thread pool, of 1..max_pieces
  * pieces each (short and long passes alternating); returns the number of pieces that did not run exactly once
  * in their own pass or were still running when their pass returned (0 when the pool is sound).  No device. */
