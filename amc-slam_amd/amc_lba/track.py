@@ -1,5 +1,7 @@
 """Tracking-side pose optimisation (Optimizer::PoseGPOptimizationFromeLastFrame, src/Optimizer.cc:369-686)
 through the C ABI (lba_tracker_*, lba_track): a batch of frames, one GPU workgroup each, one launch.
+The step before it in Tracking::TrackLocalMap, MCRansac's velocity hypotheses (src/Tracking.cc:1939-2002, one
+Optimizer::OptimizeVel each), is `Tracker.vel_ransac` / `mc_ransac` (lba_track_vel_ransac: one wave per hypothesis).
 
 `make_track_frames` cuts synthetic tracking problems out of a local-BA window: frame k's
 observations (the asynchronous cameras' GP edges between k-1 and k, the reference camera's mono /
@@ -22,6 +24,26 @@ TRACK_FRAME_DTYPE = np.dtype([
 ], align=True)
 assert TRACK_OBS_DTYPE.itemsize == 80
 assert TRACK_FRAME_DTYPE.itemsize == 272
+VEL_SET = 3
+VEL_OBS_DTYPE = np.dtype([
+    ("cam", "<i4"), ("inlier", "<i4"), ("dt", "<f8"), ("z", "<f8", (2,)), ("w", "<f8"), ("Xw", "<f8", (3,)),
+], align=True)
+VEL_FRAME_DTYPE = np.dtype([
+    ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("vel", "<f8", (6,)), ("obs0", "<i4"), ("n_obs", "<i4"),
+    ("hyp0", "<i4"), ("n_hyp", "<i4"), ("best_hyp", "<i4"), ("n_inliers", "<i4"),
+], align=True)
+assert VEL_OBS_DTYPE.itemsize == 64
+assert VEL_FRAME_DTYPE.itemsize == 128
+
+
+class LbaVelParams(ctypes.Structure):
+    """lba_vel_params; the defaults are OptimizeVel's (threshold 2.0, rk->setDelta(5.991), optimize(40))."""
+    _fields_ = [("threshold", ctypes.c_double), ("huber_delta", ctypes.c_double), ("iterations", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+def vel_params(threshold=2.0, huber_delta=5.991, iterations=40):
+    return LbaVelParams(threshold, huber_delta, iterations, 0)
 
 
 def _bind():
@@ -32,6 +54,8 @@ def _bind():
         L.lba_tracker_destroy.argtypes = [vp]
         L.lba_tracker_destroy.restype = None
         L.lba_track.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32]
+        L.lba_track_vel_ransac.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32,
+                                           ctypes.POINTER(LbaVelParams), vp, ctypes.c_int32, vp, vp, vp]
         L._track_bound = True
     return L
 
@@ -70,6 +94,121 @@ class Tracker:
         if rc != 0:
             raise LbaError(rc, "lba_track failed")
         return frames, obs
+
+    def vel_ransac(self, frames, obs, samples, cams, params=None, per_hyp=True):
+        """MCRansac's hypotheses for a batch of frames (lba_track_vel_ransac): `samples` [n_hyp, 3] frame-local
+        observation indices, `params` an LbaVelParams (vel_params(...)) or None for OptimizeVel's defaults.
+        Writes the frames (vel, best_hyp, n_inliers) and the observations' inlier flags in place and returns
+        (frames, obs, (hyp_vel [n_hyp, 6], hyp_inliers, hyp_iterations)); per_hyp=False passes NULL for the
+        per-hypothesis arrays and returns None in their place."""
+        frames = np.ascontiguousarray(frames, VEL_FRAME_DTYPE)
+        obs = np.ascontiguousarray(obs, VEL_OBS_DTYPE)
+        samples = np.ascontiguousarray(samples, np.int32).reshape(-1, VEL_SET)
+        cams = np.ascontiguousarray(cams, CAM_DTYPE)
+        n_hyp = len(samples)
+        hyp = (np.zeros((n_hyp, 6)), np.zeros(n_hyp, np.int32), np.zeros(n_hyp, np.int32)) if per_hyp else None
+        rc = _bind().lba_track_vel_ransac(self.h, ptr(frames), len(frames), ptr(obs), len(obs), ptr(samples), n_hyp,
+                                          ctypes.byref(params) if params is not None else None, ptr(cams), len(cams),
+                                          *([ptr(a) for a in hyp] if per_hyp else [None] * 3))
+        if rc != 0:
+            raise LbaError(rc, "lba_track_vel_ransac failed")
+        return frames, obs, hyp
+
+
+def mc_ransac(tracker, frames, obs, samples, cams, min_match=30, outlier=None, params=None):
+    """Tracking::MCRansac for a batch of frames with the caller's triples: the hypotheses on the GPU, then the
+    caller's rule (src/Tracking.cc:1987-2001) per frame: fewer than `min_match` inliers for the best hypothesis
+    returns 0 and leaves the frame's mvbOutlier alone, otherwise its non-inliers become outliers and the count
+    is returned.  `outlier`: mvbOutlier per observation on entry (None: all false).
+    Returns (counts [n_frames], outlier [n_obs] bool, frames, obs)."""
+    frames, obs, _ = tracker.vel_ransac(frames, obs, samples, cams, params=params, per_hyp=False)
+    out = np.zeros(len(obs), bool) if outlier is None else np.array(outlier, bool)
+    ret = np.zeros(len(frames), np.int32)
+    for f, F in enumerate(frames):
+        if F["n_inliers"] < min_match:
+            continue
+        rows = slice(int(F["obs0"]), int(F["obs0"] + F["n_obs"]))
+        out[rows] |= obs["inlier"][rows] == 0
+        ret[f] = F["n_inliers"]
+    return ret, out, frames, obs
+
+
+def _se3_exp(xi):
+    """exp of a twist [translation; rotation] as (R, t)."""
+    from .synth import _expso3
+    xi = np.asarray(xi, float)
+    w = xi[3:]
+    th = np.linalg.norm(w)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th < 1e-9:
+        V = np.eye(3) + 0.5 * K
+    else:
+        V = np.eye(3) + (1 - np.cos(th)) / th**2 * K + (th - np.sin(th)) / th**3 * (K @ K)
+    return _expso3(w), V @ xi[:3]
+
+
+def make_vel_frames(n_frames=1, n_obs=200, n_cam=4, n_hyp=23, noise=0.7, outlier_frac=0.1, seed=0, vel_true=None,
+                    start_sigma=0.05, dts=None, n_octaves=8):
+    """Synthetic MCRansac inputs: per frame a last-frame pose T (float values, like GetPoseW()), a true body
+    velocity, camera c observed `dts[c]` seconds after the last frame (default 0.08 .. 0.11 s), `n_obs` map points
+    seen from the pose T exp(v dt) of their camera with `noise` pixels of Gaussian error, a share `outlier_frac`
+    of gross outliers (20 .. 100 px off), octave weights 1 / 1.2^(2k), the start velocity `start_sigma` off the
+    truth (float values, like GetVelocity()), and `n_hyp` seeded triples of distinct observations.
+    Returns (frames, obs, samples [n_frames * n_hyp, 3], cams, truth) with truth = {"vel": [n_frames, 6],
+    "gross": bool [n_frames * n_obs]}."""
+    from .synth import _f32, _rotz, quat_to_rot, rot_to_quat
+    rng = np.random.default_rng(seed)
+    Rbc0 = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
+    yaws = [np.pi / 2, np.pi, -np.pi / 2]
+    cam_yaw = [yaws[c % 3] for c in range(n_cam - 1)] + [0.0]
+    cams = np.zeros(n_cam, CAM_DTYPE)
+    Rbc, tbc = np.zeros((n_cam, 3, 3)), np.zeros((n_cam, 3))
+    for c in range(n_cam):
+        q = _f32(rot_to_quat(_rotz(cam_yaw[c]) @ Rbc0))
+        Rbc[c] = quat_to_rot(q)
+        tbc[c] = _f32([0.5 * np.cos(cam_yaw[c]), 0.5 * np.sin(cam_yaw[c]), 0.2])
+        cams[c]["q"], cams[c]["t"] = q, tbc[c]
+        cams[c]["fx"], cams[c]["fy"], cams[c]["cx"], cams[c]["cy"] = 500.0, 500.0, 480.0, 300.0
+        cams[c]["rbc_ini"] = q
+        cams[c]["rbc_info"] = (0.2 * np.eye(3)).ravel()
+    dts = np.linspace(0.08, 0.11, n_cam) if dts is None else np.broadcast_to(np.asarray(dts, float), (n_cam,))
+    frames = np.zeros(n_frames, VEL_FRAME_DTYPE)
+    obs = np.zeros(n_frames * n_obs, VEL_OBS_DTYPE)
+    samples = np.zeros((n_frames * n_hyp, VEL_SET), np.int32)
+    truth = {"vel": np.zeros((n_frames, 6)), "gross": np.zeros(n_frames * n_obs, bool)}
+    for f in range(n_frames):
+        q = _f32(rot_to_quat(_rotz(rng.uniform(-np.pi, np.pi))))
+        R, t = quat_to_rot(q / np.linalg.norm(q)), _f32(rng.uniform(-20, 20, 3))
+        v = (np.array([4.0, 0.0, 0.0, 0.0, 0.0, 0.15]) + rng.normal(0, [0.3, 0.1, 0.05, 0.01, 0.01, 0.05])
+             if vel_true is None else np.asarray(vel_true, float))
+        truth["vel"][f] = v
+        F = frames[f]
+        F["q"], F["t"] = q, t
+        F["vel"] = _f32(v + rng.normal(0, start_sigma, 6)) if start_sigma is not None else 0.0
+        F["obs0"], F["n_obs"], F["hyp0"], F["n_hyp"] = f * n_obs, n_obs, f * n_hyp, n_hyp
+        o = obs[f * n_obs:(f + 1) * n_obs]
+        cam = rng.integers(0, n_cam, n_obs)
+        o["cam"], o["dt"] = cam, dts[cam]
+        o["w"] = 1.0 / 1.2 ** (2 * rng.integers(0, n_octaves, n_obs))
+        gross = rng.random(n_obs) < outlier_frac
+        truth["gross"][f * n_obs:(f + 1) * n_obs] = gross
+        for c in range(n_cam):
+            rows = np.nonzero(cam == c)[0]
+            Rm, tm = _se3_exp(v * dts[c])
+            Rwc, twc = R @ Rm @ Rbc[c], R @ (Rm @ tbc[c] + tm) + t       # T exp(v dt) Tbc
+            uv = np.stack([rng.uniform(20, 940, rows.size), rng.uniform(20, 580, rows.size)], axis=1)
+            depth = rng.uniform(4.0, 30.0, rows.size)
+            Xc = np.stack([(uv[:, 0] - 480.0) / 500.0 * depth, (uv[:, 1] - 300.0) / 500.0 * depth, depth], axis=1)
+            Xw = _f32(Xc @ Rwc.T + twc)
+            Xc = (Xw - twc) @ Rwc                                          # the float point, re-projected
+            z = np.stack([500.0 * Xc[:, 0] / Xc[:, 2] + 480.0, 500.0 * Xc[:, 1] / Xc[:, 2] + 300.0], axis=1)
+            z += rng.normal(0, noise, z.shape)
+            ang, far = rng.uniform(0, 2 * np.pi, rows.size), rng.uniform(20, 100, rows.size)
+            z += np.where(gross[rows, None], np.stack([far * np.cos(ang), far * np.sin(ang)], axis=1), 0.0)
+            o["Xw"][rows], o["z"][rows] = Xw, _f32(z)
+        if n_hyp:
+            samples[f * n_hyp:(f + 1) * n_hyp] = [rng.choice(n_obs, VEL_SET, replace=False) for _ in range(n_hyp)]
+    return frames, obs, samples, cams, truth
 
 
 def make_track_frames(win, ks, fix_prev=True, outlier_init=0.05, close_frac=0.2, seed=0, point_noise=0.02,

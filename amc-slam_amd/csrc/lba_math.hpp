@@ -538,6 +538,44 @@ LBA_HD void obs_j1(const double* Rwb, const CamD& c, const double* Xb, const dou
             Jp[r * 3 + j] = -(M[r * 3 + 0] * Rwb[j * 3 + 0] + M[r * 3 + 1] * Rwb[j * 3 + 1] + M[r * 3 + 2] * Rwb[j * 3 + 2]);
 }
 
+// EdgeVelReproj of Tracking::MCRansac / Optimizer::OptimizeVel (include/G2oTypes.h:521-547,
+// src/G2oTypes.cc:497-510): the point in the last frame's body frame, Xb = T^-1 Xw, is carried by the
+// constant-velocity motion, Xc = Tcb exp(-v dt) Xb, e = z - pi(Xc) (no depth test).  exp(v dt) = (Rp, tp) takes the
+// place of project_residual's pose sample with Xb as its world point: exp(-v dt) Xb = Rp^T (Xb - tp).
+LBA_HD void vel_motion(const double* v, double dt, double* Rp, double* tp) {
+    const double xi[6] = {v[0] * dt, v[1] * dt, v[2] * dt, v[3] * dt, v[4] * dt, v[5] * dt};
+    const SE3 E = se3_exp(xi);
+    qmat(E.q, Rp);
+    tp[0] = E.t[0]; tp[1] = E.t[1]; tp[2] = E.t[2];
+}
+LBA_HD void vel_reproj_error(const double* Rp, const double* tp, const CamD& c, const double* Xb, const double* z,
+                             double* Xc, double* e) {
+    double Xm[3];
+    project_residual<2>(Rp, tp, c, Xb, z, 0.0, Xm, Xc, e);
+}
+// J = P(Xc) R(Tcb exp(-v dt)) [I | -Xb^] Jr(-v dt) dt (2 x 6, row-major), Jr = RightJacobianPose3 with its
+// small-angle branches: obs_j1 with Rcb exp(-v dt) as the camera rotation, chained with Jr = [Jb, Qb; 0, Jb].
+LBA_HD void vel_reproj_jac(const double* v, double dt, const double* Rp, const CamD& c, const double* Xb,
+                           const double* Xc, double* J) {
+    CamD c1 = c;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)   // Rcb Rp^T
+            c1.Rcb[i * 3 + j] = c.Rcb[i * 3 + 0] * Rp[j * 3 + 0] + c.Rcb[i * 3 + 1] * Rp[j * 3 + 1] + c.Rcb[i * 3 + 2] * Rp[j * 3 + 2];
+    double J1[12], Jp[6], Jb[9], Qb[9];
+    obs_j1<2>(Rp, c1, Xb, Xc, 0.0, J1, Jp);
+    const double m[6] = {-v[0] * dt, -v[1] * dt, -v[2] * dt, -v[3] * dt, -v[4] * dt, -v[5] * dt};
+    right_jac_blocks(m, Jb, Qb);
+    for (int r = 0; r < 2; ++r)
+        for (int j = 0; j < 3; ++j) {
+            const double* a = J1 + r * 6;
+            const double jt = a[0] * Jb[j] + a[1] * Jb[3 + j] + a[2] * Jb[6 + j];
+            const double jr = a[0] * Qb[j] + a[1] * Qb[3 + j] + a[2] * Qb[6 + j] +
+                              (a[3] * Jb[j] + a[4] * Jb[3 + j] + a[5] * Jb[6 + j]);
+            J[r * 6 + j] = jt * dt;
+            J[r * 6 + 3 + j] = jr * dt;
+        }
+}
+
 // fp32-residual option (LBA_FLAG_F32_RESIDUAL, BASELINE configs[4]: "fp32 residuals + fp64 accumulate"): the
 // same two functions with the projection, the residual and the Jacobian rows in fp32.  The world offset Xw - twb
 // stays fp64 (a trajectory kilometres long would otherwise lose millimetres to fp32 rounding before the

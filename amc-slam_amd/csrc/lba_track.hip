@@ -22,13 +22,13 @@
 
 #include "../../include/amc_lba.h"
 #include "lba_math.hpp"
+#include "lba_tracker.hpp"
 
 using namespace lba;
 
 namespace {
 
 constexpr int TR_THREADS = 256;
-constexpr int TR_MAXS = 16;   // pose samples per frame: distinct camera time stamps + the frame's own pose
 constexpr int CAMD_N = 16;    // Rcb(9) tcb(3) fx fy cx cy
 
 struct TrackArgs {
@@ -493,17 +493,6 @@ struct HipErr {
 
 }  // namespace
 
-struct lba_tracker {
-    lba_config cfg{};
-    hipStream_t stream = nullptr;
-    lba_track_frame* d_frames = nullptr;
-    lba_track_obs* d_obs = nullptr;
-    int *d_obs_smp = nullptr, *d_smp0 = nullptr, *d_smp_obs0 = nullptr, *d_smp_kf = nullptr;
-    double *d_smp_t = nullptr, *d_camd = nullptr, *d_chi2 = nullptr;
-    size_t cap[9] = {};   // capacities of the buffers above, in elements
-    std::string err;
-};
-
 namespace {
 template <typename T>
 void grow(T*& p, size_t& cap, size_t n) {
@@ -538,7 +527,7 @@ void lba_tracker_destroy(lba_tracker* t) {
     if (!t) return;
     (void)hipSetDevice(t->cfg.device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
-    void* bufs[] = {t->d_frames, t->d_obs, t->d_obs_smp, t->d_smp0, t->d_smp_obs0, t->d_smp_kf, t->d_smp_t, t->d_camd, t->d_chi2};
+    void* bufs[] = {t->d_frames, t->d_obs, t->d_obs_smp, t->d_smp0, t->d_smp_obs0, t->d_smp_kf, t->d_smp_t, t->d_camd, t->d_chi2, t->d_vel};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (t->stream) (void)hipStreamDestroy(t->stream);

@@ -1,0 +1,24 @@
+// lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip) and
+// lba_track_vel_ransac (lba_track_vel.hip).  One stream, device buffers that grow and are reused across calls.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/amc_lba.h"
+
+constexpr int TR_MAXS = 16;   // pose samples per frame: distinct camera time stamps + the frame's own pose
+
+struct lba_tracker {
+    lba_config cfg{};
+    hipStream_t stream = nullptr;
+    lba_track_frame* d_frames = nullptr;
+    lba_track_obs* d_obs = nullptr;
+    int *d_obs_smp = nullptr, *d_smp0 = nullptr, *d_smp_obs0 = nullptr, *d_smp_kf = nullptr;
+    double *d_smp_t = nullptr, *d_camd = nullptr, *d_chi2 = nullptr;
+    size_t cap[9] = {};   // capacities of the buffers above, in elements
+    char* d_vel = nullptr;   // lba_track_vel_ransac: one arena (inputs, outputs, inlier masks)
+    size_t vel_cap = 0;      // its capacity in bytes
+    std::string err;
+};

@@ -399,6 +399,47 @@ void lba_tracker_destroy(lba_tracker* t);
 int  lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_track_obs* obs, int32_t n_obs,
                const lba_cam* cams, int32_t n_cam);
 
+/* ---- tracking: Tracking::MCRansac's hypotheses (src/Tracking.cc:1939-2002), the step before lba_track.
+ * Each hypothesis is one Optimizer::OptimizeVel (src/Optimizer.cc:2364-2447): a 6-d VertexVel (additive update,
+ * include/G2oTypes.h:128-145) started at pF1->GetVelocity(), one EdgeVelReproj per matched feature
+ * (include/G2oTypes.h:521-547, src/G2oTypes.cc:497-510: Xc = (T exp(v dt) Tbc)^-1 Xw, e = z - project(Xc), no
+ * depth test, information w I, Huber delta 5.991), only the LBA_VEL_SET sampled edges at level 0; optimize(iterations)
+ * of g2o's Levenberg (tau, max_trials, early_stop of the tracker's lba_config, no user lambda), then computeError()
+ * on every edge: inlier iff ||e|| <= threshold (pixels, unweighted; a NaN error is an outlier).  The best
+ * hypothesis of a frame is the first with strictly more inliers than every earlier one, starting from 0
+ * (Tracking.cc:1978-1984).  The caller draws the triples (std::random_device in the reference) and applies the
+ * minMatch rule (Tracking.cc:1987-2001) to n_inliers / inlier.  A batch of frames runs as two launches: one wave
+ * per hypothesis, then one per frame for the selection.
+ * LBA_E_ARG: null tracker, a camera index out of range, a triple with an index outside [0, n_obs) of its frame or
+ * with a repeated index, iterations < 0, a dt that is not finite, observation or hypothesis ranges outside the
+ * arrays.  LBA_E_LIMIT: more distinct (cam, dt) pairs in a frame than lba_track's 16 pose samples.  A refused
+ * call writes nothing.  n_hyp == 0 for a frame (best_hyp = -1) and n_frames == 0 are valid.  A hypothesis's three
+ * edges accumulate in ascending observation index.  hyp_iterations is reported, not reproducible to the count:
+ * three edges fit six unknowns exactly, chi2 falls to rounding level and the stop rules then fire on noise. */
+#define LBA_VEL_SET 3
+typedef struct lba_vel_obs {
+    int32_t cam;        /* pF1->mmpKeyToCam[index] */
+    int32_t inlier;     /* out: the best hypothesis's vbInliers[i]; 0 when there is none */
+    double  dt;         /* pF1->mvTimeStamps[cam] - pF2->mTimeStamp */
+    double  z[2];       /* mvKeysUn[index].pt */
+    double  w;          /* mvInvLevelSigma2[octave] */
+    double  Xw[3];      /* pMP->GetWorldPos() widened */
+} lba_vel_obs;
+typedef struct lba_vel_frame {
+    double  q[4], t[3]; /* pF2->GetPoseW(), (x, y, z, w) */
+    double  vel[6];     /* in: pF1->GetVelocity(); out: bestVel, untouched when best_hyp < 0 */
+    int32_t obs0, n_obs;
+    int32_t hyp0, n_hyp;          /* its triples in `samples`: frame-local obs indices */
+    int32_t best_hyp, n_inliers;  /* out: frame-local index or -1; its inlier count or 0 */
+} lba_vel_frame;
+typedef struct lba_vel_params { double threshold, huber_delta; int32_t iterations, pad; } lba_vel_params;
+int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32_t n_frames,
+                         lba_vel_obs* obs, int32_t n_obs,
+                         const int32_t* samples, int32_t n_hyp,   /* [LBA_VEL_SET * n_hyp] */
+                         const lba_vel_params* prm,               /* NULL: 2.0, 5.991, 40 */
+                         const lba_cam* cams, int32_t n_cam,
+                         double* hyp_vel, int32_t* hyp_inliers, int32_t* hyp_iterations); /* each may be NULL */
+
 #ifdef __cplusplus
 }
 #endif
