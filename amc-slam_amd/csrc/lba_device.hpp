@@ -106,7 +106,35 @@ enum { FAULT_FLOW = 1, FAULT_EXP = 2, FAULT_UPD = 4 };
 constexpr int RED_FAULT_BITS = 3;
 constexpr int RED_N = 4 + RED_FAULT_BITS;   // doubles of DevProblem::red4
 
+// k_lin_schur's inputs, packed at set-up so that a tile's operands arrive in two dependent rounds of loads (the
+// descriptor, then everything it points at) instead of four (a workgroup -> tile map -> the per-tile tables -> the observation
+// arrays -> the per-lane gathers of pose / camera / landmark / bf).
+// TileDesc: one per tile workgroup in DISPATCH order (indexed by blockIdx.x: the longest-first permutation is applied
+// when the array is built), everything the kernel read from the per-tile tables, the CSR bounds of its entry / row
+// lists already subtracted, and per tile sample its global pose sample and the KF whose bf its observations use.
+constexpr int TD_STAGED = 1;        // TileDesc::flags: a regular tile (ob_row carries the tile-local sample, the
+                                    // landmarks are [lm0, lm0 + nlm)): phase 1's operands are staged in LDS
+struct alignas(16) TileDesc {
+    int tile, obs0, nobs, ts0;
+    int nts, pair0, npair, lm0;
+    int nlm, sent0, nsent, nkf;
+    int kf0, q0, nq, m0;
+    int nm, flags, pad0, pad1;
+    int smp[TILE_SMP];              // global pose sample of tile sample i (tsm_smp[ts0 + i])
+    int bfkf[TILE_SMP];             // KF record whose bf the observations of tile sample i read
+};
+static_assert(sizeof(TileDesc) == (20 + 2 * TILE_SMP) * 4 && sizeof(TileDesc) % 16 == 0, "TileDesc layout");
+// ObsRec: one observation's static inputs (the SoA arrays stay for k_update / k_eval / k_depth and the host paths)
+struct alignas(64) ObsRec {
+    int meta, row, smp, lm;         // ob_meta, ob_row, ob_smp, ob_lm
+    int kfa, kfb, pad0, pad1;
+    double z[3], w;
+};
+static_assert(sizeof(ObsRec) == 64, "ObsRec is four 16-byte loads");
+
 struct DevProblem {
+    const TileDesc* tile_desc;   // [n_tiles] dispatch order
+    const ObsRec* ob_rec;        // [n_obs] device order
     int n_kf, n_lm, n_obs, n_gp, n_pairs, n_tiles, n_pb, np, n_prior, n_vel, n_cam;
     int npad;               // np rounded up to CHOL_NB: leading dimension of S / Lm (identity tail)
     int n_entries, n_sentries, n_ublocks;
@@ -167,7 +195,6 @@ struct DevProblem {
     const int* tile_nsent;
     const int* tile_kf0;
     const int* tile_nkf;
-    const int* tile_perm;        // k_lin_schur workgroup -> tile (longest first)
     const int* tkf_list;    // tile KF unions (pose block indices)
     const int* sent_l1;     // per Schur entry: tile-local KF index of k1 / k2
     const int* sent_l2;

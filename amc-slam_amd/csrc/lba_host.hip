@@ -1605,7 +1605,7 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
     D.ms0 = dupload(p, ms0); D.tile_sent0 = dupload(p, t_sent0);
     D.tile_nsent = dupload(p, t_nsent); D.tile_kf0 = dupload(p, t_kf0); D.tile_nkf = dupload(p, t_nkf);
     D.tkf_list = dupload(p, tkf_list);
-    {   // k_lin_schur's workgroup -> tile map: longest first by a cost estimate (list scheduling: the tiles
+    {   // k_lin_schur's workgroup -> tile order (applied to its descriptors below): longest first by a cost estimate (list scheduling: the tiles
         // outnumber the resident workgroup slots, ~1.4x at config 1, and the costly tiles, many KFs and Schur
         // entries, sit at the end of the landmark order, so in index order the last round of workgroups ran
         // long after most CUs were idle).  Cost: a non-negative least-squares fit of measured tile durations
@@ -1619,7 +1619,62 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
         // (LBA_DISPATCH_INDEX_ORDER: index order, for the tests that check the order changes no result)
         if (!std::getenv("LBA_DISPATCH_INDEX_ORDER"))
             std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return cost[x] > cost[y]; });
-        D.tile_perm = dupload(p, perm);
+        // k_lin_schur's packed inputs (lba_device.hpp): the tile descriptors in this dispatch order and one record
+        // per observation
+        std::vector<TileDesc> desc(std::max(n_tiles, 1), TileDesc{});
+        std::atomic<int> bad_tile{-1}, bad_bf{-1};
+        par_for(SETUP_PIECES, [&](int piece) {
+            for (int w = (int)((long long)n_tiles * piece / SETUP_PIECES); w < (int)((long long)n_tiles * (piece + 1) / SETUP_PIECES); ++w) {
+                const int t = perm[w];
+                TileDesc& d = desc[w];
+                d.tile = t;
+                d.obs0 = t_obs0[t]; d.nobs = t_nobs[t];
+                d.ts0 = t_smp0[t]; d.nts = t_nsmp[t];
+                d.pair0 = t_pair0[t]; d.npair = t_npair[t];
+                d.lm0 = t_lm0[t]; d.nlm = t_nlm[t];
+                d.sent0 = t_sent0[t]; d.nsent = t_nsent[t];
+                d.kf0 = t_kf0[t]; d.nkf = t_nkf[t];
+                d.q0 = pair_r0[d.pair0]; d.nq = pair_r0[d.pair0 + d.npair] - d.q0;
+                d.m0 = lm_r0[d.lm0]; d.nm = lm_r0[d.lm0 + d.nlm] - d.m0;
+                d.flags = t < n_stiles ? TD_STAGED : 0;
+                if (d.nts > TILE_SMP || d.nobs > TILE_OBS || d.nlm > TILE_LMS) {   // (tile_fits: never)
+                    bad_tile = t;
+                    continue;
+                }
+                for (int i = 0; i < d.nts; ++i) d.smp[i] = tsm_smp[d.ts0 + i];
+                // bf keyframe per tile sample (ob_row >> 16: the observation's tile sample, regular tiles only).  All
+                // observations of a pose sample read the bf of one keyframe: a GP sample belongs to one pair, so to
+                // one KF a, and a KF pose sample is n_gps + KF b.  Checked, since the kernel relies on it.
+                if (d.flags & TD_STAGED) {
+                    for (int i = 0; i < d.nts; ++i) d.bfkf[i] = -1;
+                    for (int q = d.obs0; q < d.obs0 + d.nobs; ++q) {
+                        const int kf = (ob_meta[q] & 15) <= LBA_STEREO_GP ? ob_kfa[q] : ob_kfb[q];
+                        int& slot = d.bfkf[ob_row[q] >> 16];
+                        if (slot >= 0 && slot != kf) bad_bf = t;
+                        slot = kf;
+                    }
+                    for (int i = 0; i < d.nts; ++i)
+                        if (d.bfkf[i] < 0) bad_bf = t;   // (a tile sample without an observation)
+                }
+            }
+        });
+        if (bad_tile >= 0)
+            throw ApiError{LBA_E_LIMIT, "internal: tile " + std::to_string(bad_tile.load()) + " exceeds the tile limits"};
+        if (bad_bf >= 0)
+            throw ApiError{LBA_E_LIMIT, "internal: the observations of a pose sample of tile " + std::to_string(bad_bf.load()) +
+                                            " disagree on their bf keyframe"};
+        std::vector<ObsRec> rec(std::max(n_obs, 1), ObsRec{});
+        par_for(SETUP_PIECES, [&](int piece) {
+            for (int q = (int)((long long)n_obs * piece / SETUP_PIECES); q < (int)((long long)n_obs * (piece + 1) / SETUP_PIECES); ++q) {
+                ObsRec& r = rec[q];
+                r.meta = ob_meta[q]; r.row = ob_row[q]; r.smp = ob_smp[q]; r.lm = ob_lm[q];
+                r.kfa = ob_kfa[q]; r.kfb = ob_kfb[q];
+                for (int i = 0; i < 3; ++i) r.z[i] = ob_z[3 * (size_t)q + i];
+                r.w = ob_w[q];
+            }
+        });
+        D.tile_desc = dupload(p, desc);
+        D.ob_rec = dupload(p, rec);
     }
     D.n_stiles = n_stiles; D.n_heavy = n_heavy;
     D.hv_lm = dupload(p, hv_lm); D.hv_seg0 = dupload(p, hv_seg0); D.hv_hp0 = dupload(p, hv_hp0);

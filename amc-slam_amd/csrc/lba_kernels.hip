@@ -213,15 +213,12 @@ __device__ __forceinline__ double obs_pose(const double* gps, const double* kst,
 // One observation of the linearisation (DIM compile-time so every per-row array stays in
 // registers): residual, Huber weight, the rows [J1 e Jp] into the LDS row buffer (J1 w.r.t. the
 // pose sample: the pose / velocity Jacobian J1 N is never formed, see k_linearize); returns rho(chi2).
+// cd / (Rwb, twb) / bf / Xw: the observation's camera, body pose, stereo bf and landmark, in registers (k_lin_schur
+// takes them from its LDS staging or, for segment tiles and many cameras, from global memory); row: its first LDS row
 template <int DIM, bool F32 = false>
-__device__ __forceinline__ double lin_obs(const DevProblem& P, const double* gps, const double* kst, const double* lst,
-                                          const double* camd, int o, const ObsIn& in, int cam, bool gp, double* rows,
+__device__ __forceinline__ double lin_obs(const DevProblem& P, const CamD& cd, const double* Rwb, const double* twb,
+                                          double bf, const double* Xw, int o, const ObsIn& in, int row, double* rows,
                                           double* rw, int write_res) {
-    CamD cd;
-    load_cam(camd + (size_t)cam * CAMD_STRIDE, &cd);
-    double Rwb[9], twb[3];
-    const double bf = obs_pose(gps, kst, in, gp, Rwb, twb);
-    const double* Xw = lst + (size_t)in.lm * 3;
     double z[DIM];
 #pragma unroll
     for (int d = 0; d < DIM; ++d) z[d] = in.z[d];
@@ -236,7 +233,6 @@ __device__ __forceinline__ double lin_obs(const DevProblem& P, const double* gps
     double J1[6 * DIM], Jp[3 * DIM];
     obs_j1_p<DIM, F32>(Rwb, cd, Xb, Xc, bf, J1, Jp);
     const double s = r1 * w;   // robustInformation = rho' * Omega (base_edge.h:96-102), Omega = w I
-    const int row = P.ob_row[o] & 0xffff;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) {
         double* R = rows + (row + d) * ROW_STRIDE;
@@ -745,6 +741,16 @@ constexpr int PIDX_STRIDE = TILE_LMS + 2;
 constexpr int DL_STRIDE = 12;   // per landmark in LDS: l10 l21 (l10 l21 - l20) 0 | D^-1 (3) 0 | u (3) 0
 static_assert(TILE_ROWS * (ROW_STRIDE + 1) <= LS_U, "the LDS rows alias the Hpl staging");
 static_assert(EDGE_SHM <= LS_U, "edge items run in the tile LDS");
+// phase 1's staged operands (the tile's sample poses, landmarks, bf and the cameras' projection records) live in the
+// part of U that the rows and weights do not use, from ST_BASE
+constexpr int ST_CAMS = 8;        // cameras staged in LDS (16 doubles each); more: phase 1 loads its camera per lane
+constexpr int ST_LANES = 7;       // staging lanes per tile sample: six 16-byte pieces of Rwb twb, one for bf
+constexpr int ST_PASSES = (ST_LANES * TILE_SMP + LS_THREADS - 1) / LS_THREADS;
+constexpr int ST_BASE = TILE_ROWS * (ROW_STRIDE + 1);
+static_assert(ST_BASE % 2 == 0 && KFP_STRIDE % 2 == 0 && GPS_STRIDE % 2 == 0, "16-byte pieces of a sample pose");
+static_assert(ST_BASE + TILE_SMP * KFP_STRIDE + TILE_LMS * 3 + ST_CAMS * 16 + TILE_SMP <= LS_U,
+              "phase 1's staged operands fit beside the rows");
+static_assert(3 * TILE_LMS <= LS_THREADS && 16 * ST_CAMS <= LS_THREADS, "one staged landmark / camera double per thread");
 static_assert(2 * TILE_PAIRS <= LS_THREADS && TILE_KF * TILE_KF <= LS_THREADS && TILE_SENT <= LS_THREADS &&
                   TILE_LMS <= LS_THREADS && 2 * TILE_SMP <= LS_THREADS && TILE_PROWS <= LS_THREADS,
               "one staging element / Hpl half / KF-pair slot per thread");
@@ -753,7 +759,7 @@ static_assert(2 * TILE_PAIRS <= LS_THREADS && TILE_KF * TILE_KF <= LS_THREADS &&
 template <bool F32>
 __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int sel, int gate, double lambda_arg,
                                                              int mode) {
-    __shared__ double U[LS_U];
+    __shared__ __attribute__((aligned(16))) double U[LS_U];
     __shared__ double Dl[TILE_LMS * DL_STRIDE];  // per landmark: L^-T terms, D^-1, u = D^-1 L^-1 bl (DL_STRIDE)
     __shared__ int tsm[2 * TILE_SMP];
     __shared__ int osm[TILE_OBS];
@@ -787,45 +793,117 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
         edge_item<LS_THREADS>(P, sel, blockIdx.x - P.n_tiles, tid, U);
         return;
     }
-    const int tile = P.tile_perm[blockIdx.x];
-    const int obs0 = P.tile_obs0[tile], nobs = P.tile_nobs[tile];
-    const int ts0 = P.tile_smp0[tile], nts = P.tile_nsmp[tile];
-    const int pair0 = P.tile_pair0[tile], npair = P.tile_npair[tile];
-    const int lm0 = P.tile_lm0[tile], nlm = P.tile_nlm[tile];
-    const bool elim = (mode & LS_SCHUR) && tile < P.n_stiles;
+    // ---- load round 1: what depends on the workgroup index alone.  The tile's descriptor (its header is read by every
+    //      lane at one address, as 16-byte loads), per staging lane the pose sample and bf keyframe it will fetch, and
+    //      the cameras' projection records (at most ST_CAMS of them; with more, phase 1 loads its own per lane)
+    const TileDesc& __restrict__ td = P.tile_desc[blockIdx.x];
     const int si = state_idx(P, sel);
     const double* __restrict__ kst = P.kbuf[si];
     const double* __restrict__ lst = P.lbuf[si];
     const double* __restrict__ gps = P.gpsb[si];
-    const double* __restrict__ camd = P.camdb[si];
+    const double* __restrict__ camd = P.camdb[si];   // (this state buffer's: free extrinsics differ between the two)
+    int st_smp[ST_PASSES], st_kf[ST_PASSES];
+#pragma unroll
+    for (int k = 0; k < ST_PASSES; ++k) {
+        const int s = min((tid + k * LS_THREADS) / ST_LANES, TILE_SMP - 1);
+        st_smp[k] = td.smp[s];
+        st_kf[k] = td.bfkf[s];
+    }
+    const bool cam_lds = P.n_cam <= ST_CAMS;
+    double st_cam = 0.0;
+    if (cam_lds && tid < 16 * P.n_cam) st_cam = camd[(size_t)(tid >> 4) * CAMD_STRIDE + (tid & 15)];
+    // (the header's values are the same in every lane: kept in scalar registers for the whole kernel)
+#define TD_FIELD(f) __builtin_amdgcn_readfirstlane(td.f)
+    const int tile = TD_FIELD(tile);
+    const int obs0 = TD_FIELD(obs0), nobs = TD_FIELD(nobs);
+    const int ts0 = TD_FIELD(ts0), nts = TD_FIELD(nts);
+    const int pair0 = TD_FIELD(pair0), npair = TD_FIELD(npair);
+    const int lm0 = TD_FIELD(lm0), nlm = TD_FIELD(nlm);
+    const int td_sent0 = TD_FIELD(sent0), td_nsent = TD_FIELD(nsent), td_nkf = TD_FIELD(nkf), td_kf0 = TD_FIELD(kf0);
+    const int td_q0 = TD_FIELD(q0), td_nq = TD_FIELD(nq), td_m0 = TD_FIELD(m0), td_nm = TD_FIELD(nm);
+    const bool staged = TD_FIELD(flags) & TD_STAGED;
+#undef TD_FIELD
+    const bool elim = (mode & LS_SCHUR) && tile < P.n_stiles;
     double* rows = U;
     double* rw = U + TILE_ROWS * ROW_STRIDE;
+    // phase 1's operands, staged in the part of U its rows and weights leave free (dead before U takes Hpl)
+    double* s_pose = U + ST_BASE;                    // [TILE_SMP][KFP_STRIDE] Rwb twb by tile sample
+    double* s_lm = s_pose + TILE_SMP * KFP_STRIDE;   // [TILE_LMS][3] by tile landmark
+    double* s_cam = s_lm + TILE_LMS * 3;             // [ST_CAMS][16] by camera
+    double* s_bf = s_cam + ST_CAMS * 16;             // [TILE_SMP] by tile sample
     if (P.tdbg_lin && tid == 0) P.tdbg_lin[(size_t)tile * 16 + 12] = __builtin_amdgcn_s_memrealtime();
     LBA_TMARKI(P.tdbg_lin, tile, 0);
 
-    // ---- stage the tile's index lists in LDS
-    {
-        const int q0 = P.pair_r0[pair0], nq = P.pair_r0[pair0 + npair] - q0;
-        const int m0 = P.lm_r0[lm0], nm = P.lm_r0[lm0 + nlm] - m0;
-        if (tid < 2 * nts) tsm[tid] = P.tsm_meta[2 * (size_t)ts0 + tid];
-        if (tid < nq) prow[tid] = P.pair_rows[q0 + tid];
+    // ---- load round 2, all issued together and only then stored (a load that is followed by its own LDS store is
+    //      waited for before the next one is issued: one round trip per list): every lane's observation record, the
+    //      tile's sample poses / bf and landmarks (regular tiles; a sample: six 16-byte pieces of its pose and its
+    //      keyframe's bf, bytes 112..127 of the record, one lane each), and the index lists of the later phases
+    constexpr int LR_PASSES = (TILE_ROWS + LS_THREADS - 1) / LS_THREADS;
+    const int q0 = td_q0, nq = td_nq;
+    const int m0 = td_m0, nm = td_nm;
+    ObsRec rc;
+    if (tid < nobs) rc = P.ob_rec[obs0 + tid];
+    dbl2 v_st[ST_PASSES];
+    double v_lm = 0.0;
+    int v_tsm = 0, v_prow = 0, v_lrow[LR_PASSES], v_pr0 = 0, v_lr0 = 0;
+    if (staged) {
 #pragma unroll
-        for (int k = 0; k < (TILE_ROWS + LS_THREADS - 1) / LS_THREADS; ++k) {
+        for (int k = 0; k < ST_PASSES; ++k) {
             const int t = tid + k * LS_THREADS;
-            if (t < nm) lrow[t] = P.lm_rows[m0 + t];
+            const int s = t / ST_LANES, part = t - ST_LANES * s;
+            if (t < ST_LANES * nts)
+                v_st[k] = *reinterpret_cast<const dbl2*>(part < ST_LANES - 1
+                                                             ? gps + (size_t)st_smp[k] * GPS_STRIDE + 2 * part
+                                                             : kst + (size_t)st_kf[k] * KF_STRIDE + 14);
         }
-        if (tid <= npair) pr0[tid] = P.pair_r0[pair0 + tid] - q0;
-        if (tid <= nlm) lr0[tid] = P.lm_r0[lm0 + tid] - m0;
-        if (elim)
-            for (int t = tid; t < PIDX_STRIDE * TILE_KF; t += LS_THREADS) pidx[t] = (short)npair;
+        if (tid < 3 * nlm) v_lm = lst[3 * (size_t)lm0 + tid];
     }
+    if (tid < 2 * nts) v_tsm = P.tsm_meta[2 * (size_t)ts0 + tid];
+    if (tid < nq) v_prow = P.pair_rows[q0 + tid];
+#pragma unroll
+    for (int k = 0; k < LR_PASSES; ++k) {
+        const int t = tid + k * LS_THREADS;
+        v_lrow[k] = 0;
+        if (t < nm) v_lrow[k] = P.lm_rows[m0 + t];
+    }
+    if (tid <= npair) v_pr0 = P.pair_r0[pair0 + tid];
+    if (tid <= nlm) v_lr0 = P.lm_r0[lm0 + tid];
+    if (elim)
+        for (int t = tid; t < PIDX_STRIDE * TILE_KF; t += LS_THREADS) pidx[t] = (short)npair;
+    if (staged) {
+#pragma unroll
+        for (int k = 0; k < ST_PASSES; ++k) {
+            const int t = tid + k * LS_THREADS;
+            const int s = t / ST_LANES, part = t - ST_LANES * s;
+            if (t < ST_LANES * nts) {
+                if (part < ST_LANES - 1) *reinterpret_cast<dbl2*>(s_pose + s * KFP_STRIDE + 2 * part) = v_st[k];
+                else s_bf[s] = v_st[k].x;
+            }
+        }
+        if (tid < 3 * nlm) s_lm[tid] = v_lm;
+    }
+    if (cam_lds && tid < 16 * P.n_cam) s_cam[tid] = st_cam;
+    if (tid < 2 * nts) tsm[tid] = v_tsm;
+    if (tid < nq) prow[tid] = v_prow;
+#pragma unroll
+    for (int k = 0; k < LR_PASSES; ++k) {
+        const int t = tid + k * LS_THREADS;
+        if (t < nm) lrow[t] = v_lrow[k];
+    }
+    if (tid <= npair) pr0[tid] = v_pr0 - q0;
+    if (tid <= nlm) lr0[tid] = v_lr0 - m0;
 
     // ---- phase 1: one observation per lane: residual, robust weight, rows [J1 e Jp] -> LDS
+    __syncthreads();   // the staged operands are in LDS
     double rho0 = 0.0;
     if (tid < nobs) {
         const int o = obs0 + tid;
-        const int meta = P.ob_meta[o], orw = P.ob_row[o];
-        const ObsIn in = obs_in(P, o);
+        const int meta = rc.meta, orw = rc.row;
+        ObsIn in;
+        in.kfa = rc.kfa; in.kfb = rc.kfb; in.smp = rc.smp; in.lm = rc.lm;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) in.z[d] = rc.z[d];
+        in.w = rc.w;
         const int kind = meta & 15, cam = meta >> 4;
         const bool gp = kind <= LBA_STEREO_GP;
         osm[tid] = in.smp;
@@ -833,14 +911,34 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
         const bool st = kind == LBA_STEREO_GP || kind == LBA_STEREO;
         orow[tid] = (orw & 0xffff) | ((st ? 3 : 2) << 16);
         const int wr = (mode & LS_RES) ? 1 : 0;
-        rho0 = st ? lin_obs<3, F32>(P, gps, kst, lst, camd, o, in, cam, gp, rows, rw, wr)
-                  : lin_obs<2, F32>(P, gps, kst, lst, camd, o, in, cam, gp, rows, rw, wr);
+        CamD cd;
+        if (cam_lds) load_cam(s_cam + cam * 16, &cd);
+        else load_cam(camd + (size_t)cam * CAMD_STRIDE, &cd);
+        double Rwb[9], twb[3], Xw[3], bf;
+        if (staged) {   // by the tile-local sample (ob_row >> 16) and landmark
+            const int sl = orw >> 16;
+            const double* S = s_pose + sl * KFP_STRIDE;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Rwb[i] = S[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) twb[i] = S[9 + i];
+            bf = s_bf[sl];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Xw[i] = s_lm[(in.lm - lm0) * 3 + i];
+        } else {
+            bf = obs_pose(gps, kst, in, gp, Rwb, twb);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Xw[i] = lst[(size_t)in.lm * 3 + i];
+        }
+        const int row = orw & 0xffff;
+        rho0 = st ? lin_obs<3, F32>(P, cd, Rwb, twb, bf, Xw, o, in, row, rows, rw, wr)
+                  : lin_obs<2, F32>(P, cd, Rwb, twb, bf, Xw, o, in, row, rows, rw, wr);
     }
     const double tchi = block_sum<LS_THREADS>(rho0, red);   // (its barrier also publishes rows / lists)
     if (tid == 0) P.chi_lin[tile] = tchi;
-    const int nsent = elim ? P.tile_nsent[tile] : 0;
+    const int nsent = elim ? td_nsent : 0;
     if (elim) {   // the elimination's tables (the clearing of pidx was ordered by that barrier)
-        const int sent0 = P.tile_sent0[tile];
+        const int sent0 = td_sent0;
         if (tid < nsent) {
             scode[tid] = P.sent_l1[sent0 + tid] | (P.sent_l2[sent0 + tid] << 8);
             sslt[tid] = P.sslot[sent0 + tid];
@@ -927,6 +1025,11 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
             const double* Nc = side < 2 ? gps + (size_t)osm[ol] * GPS_STRIDE + 12 + 6 * (12 * side + 6 * half)
                                         : camd + (size_t)ocam[ol] * CAMD_STRIDE + 16 + 6 * (6 * half);
             const int r0 = orow[ol] & 0xffff, nrw = orow[ol] >> 16;
+            // the first three columns of the entry's N, loaded ahead of the G accumulation (their latency runs under
+            // its LDS reads and FMAs; all six columns cost 24 more bytes of scratch per lane and were not measured)
+            double nn[18];
+#pragma unroll
+            for (int u = 0; u < 18; ++u) nn[u] = Nc[u];
             double g[18];   // G = rho' w sum_rows J1^T Jp of the observation, from its LDS rows
 #pragma unroll
             for (int u = 0; u < 18; ++u) g[u] = 0.0;
@@ -949,7 +1052,7 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
             for (int i = 0; i < 6; ++i) {
                 double n[6];
 #pragma unroll
-                for (int l = 0; l < 6; ++l) n[l] = Nc[6 * i + l];
+                for (int l = 0; l < 6; ++l) n[l] = i < 3 ? nn[6 * i + l] : Nc[6 * i + l];
 #pragma unroll
                 for (int a = 0; a < 3; ++a)
                     hacc[i * 3 + a] = fma(n[5], g[15 + a], fma(n[4], g[12 + a], fma(n[3], g[9 + a],
@@ -1000,7 +1103,7 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
     //      the same order, so a wave's LDS reads of one step hit one landmark's pairs (broadcasts, few
     //      bank conflicts) and D_m^-1 is one broadcast read.  Every entry takes 8 consecutive lanes (a diagonal
     //      entry's rows 6..11 x columns 0..5 too, though never assembled), which store its slot line by line (spos_of)
-    const int nkf = P.tile_nkf[tile];
+    const int nkf = td_nkf;
     //      A last pass of at most LS_THREADS / 2 tasks (8 KFs' 36 entries leave one of 32) is split over lane pairs,
     //      lane h of a pair taking columns 3 h .. 3 h + 2 of its task's six (each output: the same landmark order
     //      and fma nest), so it costs about half a pass; the pair then swaps its blocks and lane h stores lines
@@ -1080,7 +1183,7 @@ __global__ __launch_bounds__(LS_THREADS, 3) void k_lin_schur(DevProblem P, int s
     // ---- phase 7: rhs partials: sum over the KF's landmarks of V(m,k) bl_m = W(m,k) u_m
     //      (block_solver.hpp:395-401); absent pairs read the zero pair
     {
-        const int kf0 = P.tile_kf0[tile];
+        const int kf0 = td_kf0;
         // (tasks counted from the top lane: phase 6's last pass fills the lanes from the bottom)
         for (int task = LS_THREADS - 1 - tid; task < nkf * 12; task += LS_THREADS) {
             const int l = task / 12, r = task - 12 * l;
