@@ -739,4 +739,175 @@ LBA_HD void huber(double e, double delta, double* r0, double* r1) {
     else { const double s = sqrt(e); *r0 = 2 * s * delta - d2; *r1 = delta / s; }
 }
 
+// ---------------------------------------------------------------- Sim3 (Optimizer::OptimizeSim3, lba_sim3.hip)
+// g2o::Sim3 (Thirdparty/g2o/g2o/types/sim3.h): x -> s (r x) + t.  The reference never renormalises r; here r is a
+// unit quaternion after every constructor and product (the difference is the drift of a slightly non-unit
+// quaternion, below 1e-9 over an OptimizeSim3 call).
+struct Sim3 { Quat q; double t[3]; double s; };
+
+// Eigen's Quaternion(Matrix3) (Eigen/src/Geometry/Quaternion.h, quaternionbase_assign_impl<Other, 3, 3>), not normalised
+template <int I>   // its branch for a non-positive trace, i = I the largest diagonal entry (constant indices: registers)
+LBA_HD Quat quat_from_mat_diag(const double* m) {
+    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+    double t = sqrt(m[I * 4] - m[J * 4] - m[K * 4] + 1.0);
+    double v[3];
+    v[I] = 0.5 * t;
+    t = 0.5 / t;
+    v[J] = (m[J * 3 + I] + m[I * 3 + J]) * t;
+    v[K] = (m[K * 3 + I] + m[I * 3 + K]) * t;
+    return Quat{v[0], v[1], v[2], (m[K * 3 + J] - m[J * 3 + K]) * t};
+}
+LBA_HD Quat quat_from_mat(const double* m) {
+    double t = m[0] + m[4] + m[8];
+    if (t > 0.0) {
+        t = sqrt(t + 1.0);
+        const double h = 0.5 / t;
+        return Quat{(m[7] - m[5]) * h, (m[2] - m[6]) * h, (m[3] - m[1]) * h, 0.5 * t};
+    }
+    if (m[4] > m[0]) return m[8] > m[4] ? quat_from_mat_diag<2>(m) : quat_from_mat_diag<1>(m);
+    return m[8] > m[0] ? quat_from_mat_diag<2>(m) : quat_from_mat_diag<0>(m);
+}
+
+// Sim3(const Vector7d& update), sim3.h:70-142, update = [omega; upsilon; sigma]: the four branches of A, B, C at
+// eps = 1e-5 on |sigma| and theta; in the two small-angle branches R = I + Omega + Omega^2 (as written there: not
+// 1/2 Omega^2, not orthonormal); r = Quaterniond(R), t = (A Omega + B Omega^2 + C I) upsilon, s = exp(sigma)
+LBA_HD Sim3 sim3_exp(const double* u) {
+    const double sigma = u[6];
+    const double theta = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    double Om[9], Om2[9], R[9];
+    hat3(u, Om);
+    mul33(Om, Om, Om2);
+    Sim3 S;
+    S.s = exp(sigma);
+    const double eps = 0.00001;
+    double A, B, C, ra, rb;   // R = I + ra Omega + rb Omega^2
+    if (fabs(sigma) < eps) {
+        C = 1.0;
+        if (theta < eps) {
+            A = 1. / 2.;
+            B = 1. / 6.;
+            ra = 1.0; rb = 1.0;
+        } else {
+            const double theta2 = theta * theta;
+            A = (1 - cos(theta)) / theta2;
+            B = (theta - sin(theta)) / (theta2 * theta);
+            ra = sin(theta) / theta; rb = (1 - cos(theta)) / (theta * theta);
+        }
+    } else {
+        C = (S.s - 1) / sigma;
+        if (theta < eps) {
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1) * S.s + 1) / sigma2;
+            B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+            ra = 1.0; rb = 1.0;
+        } else {
+            ra = sin(theta) / theta; rb = (1 - cos(theta)) / (theta * theta);
+            const double a = S.s * sin(theta), b = S.s * cos(theta);
+            const double theta2 = theta * theta, sigma2 = sigma * sigma;
+            const double c = theta2 + sigma2;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
+        }
+    }
+    for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + ra * Om[i] + rb * Om2[i];
+    S.q = qnormalize(quat_from_mat(R));
+    double W[9];
+    for (int i = 0; i < 9; ++i) W[i] = A * Om[i] + B * Om2[i] + (i % 4 == 0 ? C : 0.0);
+    mul33v(W, u + 3, S.t);
+    return S;
+}
+// operator* (sim3.h:266-272): r = a.r b.r, t = a.s (a.r b.t) + a.t, s = a.s b.s
+LBA_HD Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
+    Sim3 r;
+    r.q = qmul(a.q, b.q);
+    double v[3];
+    qrot(a.q, b.t, v);
+    for (int i = 0; i < 3; ++i) r.t[i] = a.s * v[i] + a.t[i];
+    r.s = a.s * b.s;
+    return r;
+}
+// inverse() (sim3.h:233-236): (r*, r* ((-1 / s) t), 1 / s)
+LBA_HD Sim3 sim3_inv(const Sim3& a) {
+    Sim3 r;
+    r.q = Quat{-a.q.x, -a.q.y, -a.q.z, a.q.w};
+    const double m = -1. / a.s;
+    const double v[3] = {m * a.t[0], m * a.t[1], m * a.t[2]};
+    qrot(r.q, v, r.t);
+    r.s = 1. / a.s;
+    return r;
+}
+// map() (sim3.h:144-146)
+LBA_HD void sim3_map(const Sim3& a, const double* x, double* o) {
+    double v[3];
+    qrot(a.q, x, v);
+    for (int i = 0; i < 3; ++i) o[i] = a.s * v[i] + a.t[i];
+}
+
+// The state both edges are evaluated at: S12 as rotation matrix, translation and scale
+struct Sim3M { double R[9], t[3], s; };
+LBA_HD Sim3M sim3_matrix(const Sim3& S) {
+    Sim3M M;
+    qmat(S.q, M.R);
+    M.t[0] = S.t[0]; M.t[1] = S.t[1]; M.t[2] = S.t[2];
+    M.s = S.s;
+    return M;
+}
+// Tcb of an lba_sim3_cam as CamD (g2o::SE3Quat normalises its rotation); body point Y = Tcb^-1 Xc
+LBA_HD void sim3_cam_derive(const double* q, const double* t, double fx, double fy, double cx, double cy, CamD* d) {
+    qmat(qnormalize(Quat{q[0], q[1], q[2], q[3]}), d->Rcb);
+    d->tcb[0] = t[0]; d->tcb[1] = t[1]; d->tcb[2] = t[2];
+    d->fx = fx; d->fy = fy; d->cx = cx; d->cy = cy;
+}
+LBA_HD void sim3_body_point(const CamD& c, const double* Xc, double* Y) {
+    const double d[3] = {Xc[0] - c.tcb[0], Xc[1] - c.tcb[1], Xc[2] - c.tcb[2]};
+    mul33tv(c.Rcb, d, Y);
+}
+// e = z - pi(Rcb X + tcb) and, if J, sign * Jproj Rcb M [ -[P]x | I | P ] (2 x 7, row-major; M may be NULL = I)
+LBA_HD void sim3_project(const CamD& c, const double* X, const double* z, const double* M, const double* P, double sign,
+                         bool fix_scale, double* e, double* J) {
+    double Xc[3];
+    mul33v(c.Rcb, X, Xc);
+    Xc[0] += c.tcb[0]; Xc[1] += c.tcb[1]; Xc[2] += c.tcb[2];
+    const double iz = 1.0 / Xc[2];
+    e[0] = z[0] - (c.fx * Xc[0] * iz + c.cx);
+    e[1] = z[1] - (c.fy * Xc[1] * iz + c.cy);
+    if (!J) return;
+    const double Jp[6] = {c.fx * iz, 0.0, -c.fx * Xc[0] * iz * iz, 0.0, c.fy * iz, -c.fy * Xc[1] * iz * iz};
+    double A[6], B[6];
+    matmul(Jp, c.Rcb, A, 2, 3, 3);
+    if (M) matmul(A, M, B, 2, 3, 3);
+    for (int r = 0; r < 2; ++r) {
+        const double* a = M ? B + 3 * r : A + 3 * r;
+        double* j = J + 7 * r;
+        j[0] = sign * (a[2] * P[1] - a[1] * P[2]);
+        j[1] = sign * (a[0] * P[2] - a[2] * P[0]);
+        j[2] = sign * (a[1] * P[0] - a[0] * P[1]);
+        j[3] = sign * a[0]; j[4] = sign * a[1]; j[5] = sign * a[2];
+        j[6] = fix_scale ? 0.0 : sign * (a[0] * P[0] + a[1] * P[1] + a[2] * P[2]);
+    }
+}
+// EdgeSim3ProjectXYZ (include/OptimizableTypes.h:176-201): Y2 = Tc2b^-1 X2c in body 2, P = S12 Y2 in body 1,
+// e = z1 - pi1(Tc1b P); J12 = -Jproj Rc1b [ -[P]x | I | P ] for the left update S <- Sim3(d) S (column 6 zero
+// under fix_scale).  J may be NULL.
+LBA_HD void sim3_edge12(const Sim3M& S, const CamD& c1, const double* Y2, const double* z1, bool fix_scale, double* e,
+                        double* J) {
+    double P[3];
+    mul33v(S.R, Y2, P);
+    for (int i = 0; i < 3; ++i) P[i] = S.s * P[i] + S.t[i];
+    sim3_project(c1, P, z1, nullptr, P, -1.0, fix_scale, e, J);
+}
+// EdgeInverseSim3ProjectXYZ (include/OptimizableTypes.h:203-229): Y1 = Tc1b^-1 X1c in body 1, Q = S12^-1 Y1
+// = (1 / s) R12^T (Y1 - t), e = z2 - pi2(Tc2b Q); S'^-1 = S^-1 Sim3(-d), so J21 = +Jproj Rc2b (1 / s) R12^T [ -[Y1]x | I | Y1 ]
+LBA_HD void sim3_edge21(const Sim3M& S, const CamD& c2, const double* Y1, const double* z2, bool fix_scale, double* e,
+                        double* J) {
+    const double is = 1.0 / S.s;
+    const double d[3] = {Y1[0] - S.t[0], Y1[1] - S.t[1], Y1[2] - S.t[2]};
+    double Q[3], M[9];
+    mul33tv(S.R, d, Q);
+    for (int i = 0; i < 3; ++i) Q[i] *= is;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) M[i * 3 + j] = is * S.R[j * 3 + i];
+    sim3_project(c2, Q, z2, M, Y1, 1.0, fix_scale, e, J);
+}
+
 }  // namespace lba

@@ -1,5 +1,6 @@
-// lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip) and
-// lba_track_vel_ransac (lba_track_vel.hip).  One stream, device buffers that grow and are reused across calls.
+// lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip),
+// lba_track_vel_ransac (lba_track_vel.hip) and lba_sim3_optimize (lba_sim3.hip).  One stream, device buffers that
+// grow and are reused across calls.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,7 +19,17 @@ struct lba_tracker {
     int *d_obs_smp = nullptr, *d_smp0 = nullptr, *d_smp_obs0 = nullptr, *d_smp_kf = nullptr;
     double *d_smp_t = nullptr, *d_camd = nullptr, *d_chi2 = nullptr;
     size_t cap[9] = {};   // capacities of the buffers above, in elements
-    char* d_vel = nullptr;   // lba_track_vel_ransac: one arena (inputs, outputs, inlier masks)
-    size_t vel_cap = 0;      // its capacity in bytes
+    char* d_vel = nullptr;   // lba_track_vel_ransac / lba_sim3_optimize: one arena per call (inputs, outputs, masks);
+    size_t vel_cap = 0;      // its capacity in bytes.  Calls on a tracker are serial, so the two share it
+    bool sim3_timed = false;             // lba_sim3_profile: bracket the launch with events
+    hipEvent_t sim3_ev[2] = {nullptr, nullptr};
+    double sim3_ms = -1.0;
+    char* h_sim3 = nullptr;              // lba_sim3_optimize: the pinned host image of its arena
+    size_t sim3_pin_cap = 0;
     std::string err;
+    ~lba_tracker() {
+        for (hipEvent_t e : sim3_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (h_sim3) (void)hipHostFree(h_sim3);
+    }
 };

@@ -440,6 +440,64 @@ int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32_t n_frames
                          const lba_cam* cams, int32_t n_cam,
                          double* hyp_vel, int32_t* hyp_inliers, int32_t* hyp_iterations); /* each may be NULL */
 
+/* ---- loop closing: Optimizer::OptimizeSim3 (src/Optimizer.cc:2049-2362) for a batch of candidate pairs (KF1, KF2),
+ * as LoopClosing.cc:381 / :597 call it once per BoW candidate.  Per pair one 7-dof VertexSim3Expmap S12
+ * (include/OptimizableTypes.h:146-173: left update S <- Sim3(update) S, tangent [omega; upsilon; sigma], sigma
+ * zeroed under fix_scale; Sim3(update) with its four branches at eps = 1e-5, Thirdparty/g2o/g2o/types/sim3.h:70-142),
+ * the map points fixed, and per correspondence the two 2-d edges in g2o's insertion order:
+ *   EdgeSim3ProjectXYZ         e = z1 - project1(Tc1b[cam1] S12      Tc2b[cam2]^-1 X2c)   (OptimizableTypes.h:176-201)
+ *   EdgeInverseSim3ProjectXYZ  e = z2 - project2(Tc2b[cam2] S12^-1   Tc1b[cam1]^-1 X1c)   (OptimizableTypes.h:203-229)
+ * pinhole in double (src/CameraModels/Pinhole.cpp:35-41), no depth test, information w I, Huber delta
+ * (double)(float)sqrt(th2) (:2115, :2234-2236).  The reference differentiates both edges numerically (their
+ * linearizeOplus is commented out: base_binary_edge.hpp:147-197, central differences of 1e-9 through oplus); the
+ * device uses the analytic Jacobian of the same left update, which that difference quotient equals up to its rounding
+ * noise.  Flow (:2285-2361): optimize(5) of g2o's Levenberg (tau, max_trials, early_stop of the
+ * tracker's lba_config, no user lambda); a correspondence is dropped when either edge's chi2() of the LAST computed
+ * errors (the last LM trial's state, accepted or not) exceeds th2, the survivors lose their robust kernel;
+ * n_corr - n_bad < 10 returns 0 with these flags written and S12 untouched; otherwise optimize(n_bad > 0 ? 10 : 5)
+ * from a fresh lambda, then the errors are recomputed, a survivor with either chi2 > th2 is flagged too, the others
+ * count into n_in, and S12 is written back.  A NaN chi2 is not > th2.  mAcumHessian (zeroed, never filled, :2337) is
+ * not exposed; the caller-side filtering of the matches (:2125-2216) is amc_lba.sim3.sim3_rows.
+ * A batch is one launch, one workgroup per pair; a pair's result does not depend on the batch or on its position.
+ * LBA_E_ARG: null tracker or arrays, n_cam < 1, a pair's correspondence range outside [0, n_corr) or camera range
+ * [cam0, cam0 + 2 n_cam) outside [0, n_cam_rows), cam1 / cam2 outside [0, n_cam), th2 not finite or <= 0, s not
+ * finite or <= 0.  LBA_E_LIMIT: a pair whose rows and cameras exceed a workgroup's 64 KB of LDS (about 600
+ * correspondences with 4 cameras).  A refused call writes nothing.  n_pairs == 0 is valid, and so is n_corr == 0 for
+ * a pair (n_in = n_bad = iterations = 0, S12 untouched).  When the correspondence ranges of two pairs overlap, the
+ * shared rows carry the flags of the later pair.  A failed 7 x 7 factorisation (non-positive pivot of the unpivoted
+ * Cholesky) is a trial with chi2 = max, as in lba_track. */
+typedef struct lba_sim3_cam {
+    double q[4], t[3];      /* Tcb of this camera of this keyframe, (vT1w[i] * T1bw^-1) widened (:2083-2088); (x, y, z, w) */
+    double fx, fy, cx, cy;  /* vpCamera1[i] / vpCamera2[i]: pinhole parameters */
+} lba_sim3_cam;
+typedef struct lba_sim3_corr {
+    int32_t cam1;           /* pKF1->mmpKeyToCam[i] (:2133) */
+    int32_t cam2;           /* the first camera of KF2 that sees pMP2 (:2140-2150) */
+    int32_t outlier;        /* out: vpMatches1[idx] was set to NULL (:2303, :2350) */
+    int32_t pad;
+    double  X1c[3];         /* vR1w[cam1] P3D1w + vt1w[cam1], widened (:2163-2165) */
+    double  X2c[3];         /* vR2w[cam2] P3D2w + vt2w[cam2], widened (:2171-2173) */
+    double  z1[2], z2[2];   /* pKF1->mvKeysUn[i].pt, pKF2->mvKeysUn[i2].pt (:2222-2224, :2246-2247) */
+    double  w1, w2;         /* mvInvLevelSigma2[octave] of either keyframe (:2231, :2270) */
+} lba_sim3_corr;
+typedef struct lba_sim3_pair {
+    double  q[4], t[3], s;  /* in: g2oS12 (:2095), (x, y, z, w); out: vSim3_recov->estimate() (:2358-2359), untouched
+                               when the early return was taken (n_corr - n_bad < 10, :2328-2329) */
+    double  th2;            /* the reference's float th2, widened */
+    int32_t fix_scale;      /* bFixScale */
+    int32_t corr0, n_corr;  /* its rows of `corr`: nCorrespondences = n_corr */
+    int32_t cam0;           /* the first of its 2 n_cam cameras in `cams`: KF1's vTc1b, then KF2's vTc2b */
+    int32_t n_in;           /* out: the return value (nIn, or 0 of the early return) */
+    int32_t n_bad;          /* out: nBad of the first pass (:2291-2320) */
+    int32_t iterations;     /* out: LM iterations of both rounds (reported; near the minimum decided by rounding) */
+    int32_t pad;
+} lba_sim3_pair;
+int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n_pairs, lba_sim3_corr* corr, int32_t n_corr,
+                      const lba_sim3_cam* cams, int32_t n_cam_rows, int32_t n_cam);
+/* Measurement only: on != 0 makes lba_sim3_optimize bracket its launch with two events on the tracker's stream;
+ * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
+int lba_sim3_profile(lba_tracker* t, int32_t on, double* last_ms);
+
 #ifdef __cplusplus
 }
 #endif
