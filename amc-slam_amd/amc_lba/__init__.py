@@ -127,7 +127,8 @@ def exported_symbols():
             "lba_group_destroy", "lba_set_partition_group", "lba_get_cams", "lba_set_farm", "lba_set_farm_rccl",
             "lba_set_farm_group", "lba_farm_plan", "lba_farm_exchange", "lba_farm_match", "lba_solver_info", "lba_solver_flops", "lba_device_bytes", "lba_setup_phases",
             "lba_kernel_modes", "lba_setup_host_profile", "lba_setup_tile_shapes", "lba_debug_pool_stress", "lba_debug_lie", "lba_partition_assign", "lba_kf_owner", "lba_split_info",
-            "lba_track_vel_ransac"]
+            "lba_track_vel_ransac", "lba_posegraph_optimize", "lba_posegraph_linearize", "lba_posegraph_step",
+            "lba_posegraph_plan_info", "lba_posegraph_profile"]
 
 
 def setup_host_profile(win, **cfg_over):

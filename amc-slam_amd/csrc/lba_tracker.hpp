@@ -1,6 +1,6 @@
 // lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip),
-// lba_track_vel_ransac (lba_track_vel.hip) and lba_sim3_optimize (lba_sim3.hip).  One stream, device buffers that
-// grow and are reused across calls.
+// lba_track_vel_ransac (lba_track_vel.hip), lba_sim3_optimize (lba_sim3.hip) and lba_posegraph_* (lba_posegraph.hip).
+// One stream, device buffers that grow and are reused across calls.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,10 +26,14 @@ struct lba_tracker {
     double sim3_ms = -1.0;
     char* h_sim3 = nullptr;              // lba_sim3_optimize: the pinned host image of its arena
     size_t sim3_pin_cap = 0;
+    char* d_pg = nullptr;                // lba_posegraph_*: the arena of a call (graph, lists, tiles, vectors)
+    size_t pg_cap = 0;
+    double pg_ms[3] = {-1.0, -1.0, -1.0};   // lba_posegraph_profile: planning, upload, device of the last optimize
     std::string err;
     ~lba_tracker() {
         for (hipEvent_t e : sim3_ev)
             if (e) (void)hipEventDestroy(e);
         if (h_sim3) (void)hipHostFree(h_sim3);
+        if (d_pg) (void)hipFree(d_pg);
     }
 };

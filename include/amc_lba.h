@@ -498,6 +498,65 @@ int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n_pairs, lba
  * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
 int lba_sim3_profile(lba_tracker* t, int32_t on, double* last_ms);
 
+/* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
+ * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
+ * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one
+ * g2o::EdgeSim3 per edge (:99-126): e = log(C S[v0] S[v1]^-1), C the measurement Sji, information I, no robust kernel;
+ * Sim3::log with its four branches at eps = 1e-5 (sim3.h:148-230).  g2o's Levenberg (tau, max_trials, early_stop of the
+ * tracker's lba_config) over a sparse Cholesky factorisation of the full system: no vertex is marginalised.  The
+ * reference differentiates EdgeSim3 numerically (central differences of 1e-9 through oplus); the device computes the
+ * analytic Jacobians J0 = Jl^-1(e) Ad(C), J1 = -Jl^-1(e) Ad(E).  The graph construction
+ * (:1504-1660) and the write-back (:1669-1713) are the caller's: amc_lba.posegraph.essential_graph / write_back.
+ *
+ * Activity follows g2o: an edge whose two vertices are fixed is inactive; a vertex that no active edge touches is
+ * inactive: it has no rows in H, b or dx and is never written.  na counts the active free vertices, in array order
+ * (pass the vertices sorted by keyframe id for g2o's order).  Several fixed vertices, parallel edges on one pair and
+ * both orientations are allowed; a block of H sums its edges' terms in edge order.  Under fix_scale the sigma row of
+ * every block of H is exactly 0 + lambda and its step is 0.  Results are bitwise reproducible, and do not depend on
+ * what the tracker ran before.
+ *
+ * LBA_E_ARG: null tracker or arrays, n_v < 1, n_e < 0, iterations < 0, an edge's vertex index outside [0, n_v),
+ * v0 == v1, a vertex's or an edge's s not finite or <= 0, a lambda that is not finite.  LBA_E_EMPTY: no active edge.
+ * LBA_E_LIMIT: more than 2^20 vertices or 2^22 edges, a graph whose lists and tiles of L exceed 6 GB of device memory,
+ * or (lba_posegraph_linearize only) more than 2048 active free vertices, whose dense H would exceed 1.6 GB.  A refused
+ * call writes nothing.
+ *
+ * lba_posegraph_optimize: lambda_init > 0 is the user lambda (the reference: 1e-16), <= 0 means tau max|H_ii|.  A
+ * failed factorisation (a non-positive pivot) is a trial with chi2 = DBL_MAX: the state is untouched and lambda
+ * grows.  Writes the active free vertices in place, `out` if not NULL, and returns the LM iterations run (>= 0).  The
+ * accept / reject decision is taken on the host: one readback of three doubles per trial.
+ * lba_posegraph_linearize: the active edges' errors (zero for an inactive edge), the dense H (no lambda) and b over the
+ * active free vertices; each of the three may be NULL.  Returns na.
+ * lba_posegraph_step: one damped step at `lambda`: dx [7 na], the trial vertices (the others copied from `v`) and
+ * the trial's chi2; each may be NULL.  Returns na, or LBA_E_SOLVE when a pivot is not positive (nothing written).
+ * lba_posegraph_plan_info: host only, no device.  info = {na, panels, tiles of L, fill-in tiles, launch levels,
+ * dependent chain (panels), loop-closure tail (panels), dissection depth}.  Returns na. */
+typedef struct lba_pg_vertex {
+    double  q[4], t[3], s;  /* in / out: Siw, (x, y, z, w) */
+    int32_t fixed, pad;
+} lba_pg_vertex;
+typedef struct lba_pg_edge {
+    int32_t v0, v1;         /* e = log(C S[v0] S[v1]^-1) */
+    double  q[4], t[3], s;  /* C: the measurement Sji */
+} lba_pg_edge;
+typedef struct lba_pg_stats {
+    int32_t iterations, trials, solve_failures, result;   /* result: 0, or 1 when the last iteration ran out of trials */
+    double  chi2_initial, chi2_final, lambda_final;
+    int32_t panels, tiles, fill_tiles, levels, chain, launches_per_solve;
+} lba_pg_stats;
+int lba_posegraph_optimize(lba_tracker* t, lba_pg_vertex* v, int32_t n_v, const lba_pg_edge* e, int32_t n_e,
+                           int32_t fix_scale, int32_t iterations, double lambda_init, lba_pg_stats* out);
+int lba_posegraph_linearize(lba_tracker* t, const lba_pg_vertex* v, int32_t n_v, const lba_pg_edge* e, int32_t n_e,
+                            int32_t fix_scale, double* errors /* [7 n_e] */, double* H /* [7 na x 7 na] */,
+                            double* b /* [7 na] */);
+int lba_posegraph_step(lba_tracker* t, const lba_pg_vertex* v, int32_t n_v, const lba_pg_edge* e, int32_t n_e,
+                       int32_t fix_scale, double lambda, double* dx /* [7 na] */, lba_pg_vertex* trial /* [n_v] */,
+                       double* chi2_trial);
+int lba_posegraph_plan_info(const lba_pg_vertex* v, int32_t n_v, const lba_pg_edge* e, int32_t n_e, int32_t info[8]);
+/* Measurement only: the host planning, upload and device (first launch to last readback) milliseconds of the
+ * tracker's last lba_posegraph_optimize. */
+int lba_posegraph_profile(lba_tracker* t, double ms[3]);
+
 #ifdef __cplusplus
 }
 #endif
