@@ -382,6 +382,19 @@ LBA_HD void cam_derive(const Cam& c, CamD* d) {
     d->fx = c.fx; d->fy = c.fy; d->cx = c.cx; d->cy = c.cy;
 }
 
+// A CamD as the tracker's kernels keep it in memory: Rcb(9) tcb(3) fx fy cx cy
+constexpr int CAMD_N = 16;
+LBA_HD void camd_store(const CamD& d, double* o) {
+    for (int i = 0; i < 9; ++i) o[i] = d.Rcb[i];
+    for (int i = 0; i < 3; ++i) o[9 + i] = d.tcb[i];
+    o[12] = d.fx; o[13] = d.fy; o[14] = d.cx; o[15] = d.cy;
+}
+LBA_HD void camd_load(const double* c, CamD* d) {
+    for (int i = 0; i < 9; ++i) d->Rcb[i] = c[i];
+    for (int i = 0; i < 3; ++i) d->tcb[i] = c[9 + i];
+    d->fx = c[12]; d->fy = c[13]; d->cx = c[14]; d->cy = c[15];
+}
+
 // Camera record of a state (CAMD_STRIDE doubles): Rcb(9) tcb(3) fx fy cx cy, then the Jacobian factor of
 // the camera's extrinsic vertex stored like a sample's N (column c at 16 + 6 c, 12 columns, the last six
 // zero: the extrinsic occupies a 12-wide pose block whose second half is inert).  EdgeMonoGPExtrinsic's

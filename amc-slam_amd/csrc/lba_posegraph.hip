@@ -26,7 +26,8 @@
 //                      the factorisation's failure word
 // and one readback of three doubles, on which the host takes g2o's accept / reject decision (a deliberate limit: a
 // call costs a few tens of readbacks).  A non-positive pivot makes the trial one with chi2 = DBL_MAX, k_track's rule.
-// Every sum has a fixed order, so results are bitwise reproducible.
+// Every sum has a fixed order, so results are bitwise reproducible.  The controller of that decision is lba_lm.hpp's,
+// the arena and the error path lba_tracker.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "../../include/amc_lba.h"
+#include "lba_lm.hpp"
 #include "lba_pg_math.hpp"
 #include "lba_plan.hpp"
 #include "lba_tracker.hpp"
@@ -463,15 +465,6 @@ int pg_plan(const lba_pg_vertex* v, int n_v, const lba_pg_edge* e, int n_e, bool
 }
 
 // ---------------------------------------------------------------------------------------------- host: the device
-struct Arena {
-    size_t total = 0;
-    size_t take(size_t bytes) {
-        const size_t o = total;
-        total += (bytes + 255) & ~size_t(255);
-        return o;
-    }
-};
-
 struct PgRun {
     lba_tracker* t = nullptr;
     PgDev D{};
@@ -491,20 +484,11 @@ void pg_pack_state(const lba_pg_vertex* v, int n_v, std::vector<double>& o) {
     }
 }
 
-#define PG_HIP(x) do { if ((x) != hipSuccess) throw 0; } while (0)
-
-// lay the arena out, grow it, upload the graph and the lists (one copy); throws 0 on a HIP error, 1 on the size limit
+// lay the arena out, grow it, upload the graph and the lists (one copy); throws TrackerError (HIP, the size limit)
 void pg_upload(lba_tracker* t, const lba_pg_vertex* v, const lba_pg_edge* e, int fix_scale, const PgHost& G, PgRun& R) {
     const int ne = (int)G.eact.size(), NP = G.NP, nt = G.pl.ntile();
-    Arena A;
-    std::vector<char> hb;
-    auto put = [&](const void* src, size_t bytes) {
-        const size_t o = A.take(bytes);
-        hb.resize(A.total, 0);
-        if (bytes) std::memcpy(hb.data() + o, src, bytes);
-        return o;
-    };
-    auto puti = [&](const std::vector<int>& a) { return put(a.data(), a.size() * sizeof(int)); };
+    ArenaImage in;
+    ArenaLayout& A = in.lay;
     std::vector<lba_pg_edge> ed(ne);
     for (int a = 0; a < ne; ++a) ed[a] = e[G.eact[a]];
     std::vector<int> jflag, jtile, joff;
@@ -514,14 +498,14 @@ void pg_upload(lba_tracker* t, const lba_pg_vertex* v, const lba_pg_edge* e, int
         joff.push_back(j.off);
     }
     pg_pack_state(v, G.n_v, R.h_state);
-    const size_t o_ed = put(ed.data(), ed.size() * sizeof(lba_pg_edge));
-    const size_t o_S = put(R.h_state.data(), R.h_state.size() * sizeof(double));
-    const size_t o_voff = puti(G.voff), o_vslot = puti(G.slot);
-    const size_t o_jptr = puti(G.job_ptr), o_jflag = puti(jflag), o_jtile = puti(jtile), o_joff = puti(joff);
-    const size_t o_con = puti(G.contrib);
-    const size_t o_lvl = puti(G.lvl_cols), o_dt = puti(G.diag_tile), o_rkp = puti(G.rk_ptr), o_rkt = puti(G.rk_tile);
-    const size_t o_rkc = puti(G.rk_col), o_crp = puti(G.cr_ptr), o_crt = puti(G.cr_tile), o_crr = puti(G.cr_row);
-    const size_t o_prp = puti(G.pr_ptr), o_pra = puti(G.pr_a), o_prb = puti(G.pr_b);
+    const size_t o_ed = in.put(ed);
+    const size_t o_S = in.put(R.h_state);
+    const size_t o_voff = in.put(G.voff), o_vslot = in.put(G.slot);
+    const size_t o_jptr = in.put(G.job_ptr), o_jflag = in.put(jflag), o_jtile = in.put(jtile), o_joff = in.put(joff);
+    const size_t o_con = in.put(G.contrib);
+    const size_t o_lvl = in.put(G.lvl_cols), o_dt = in.put(G.diag_tile), o_rkp = in.put(G.rk_ptr), o_rkt = in.put(G.rk_tile);
+    const size_t o_rkc = in.put(G.rk_col), o_crp = in.put(G.cr_ptr), o_crt = in.put(G.cr_tile), o_crr = in.put(G.cr_row);
+    const size_t o_prp = in.put(G.pr_ptr), o_pra = in.put(G.pr_a), o_prb = in.put(G.pr_b);
     const size_t up = A.total;
     const size_t o_T = A.take((size_t)G.n_v * 8 * sizeof(double));
     const size_t o_err = A.take((size_t)ne * 7 * sizeof(double)), o_J = A.take((size_t)ne * 98 * sizeof(double));
@@ -532,18 +516,12 @@ void pg_upload(lba_tracker* t, const lba_pg_vertex* v, const lba_pg_edge* e, int
     const size_t o_b = A.take(vec), o_hd = A.take(vec), o_y = A.take(vec), o_x = A.take(vec);
     const size_t o_dx = A.take((size_t)G.na * 7 * sizeof(double));
     const size_t o_out = A.take(4 * sizeof(double)), o_fail = A.take(sizeof(int));
-    if (A.total > PG_MAX_BYTES) throw 1;
-    PG_HIP(hipSetDevice(t->cfg.device));
-    if (A.total > t->pg_cap || !t->d_pg) {
-        if (t->d_pg) (void)hipFree(t->d_pg);
-        t->d_pg = nullptr;
-        t->pg_cap = 0;
-        PG_HIP(hipMalloc(reinterpret_cast<void**>(&t->d_pg), A.total + A.total / 2));
-        t->pg_cap = A.total + A.total / 2;
-    }
-    char* d = t->d_pg;
-    PG_HIP(hipMemcpyAsync(d, hb.data(), up, hipMemcpyHostToDevice, t->stream));
-    PG_HIP(hipStreamSynchronize(t->stream));   // (hb is pageable and goes out of scope)
+    if (A.total > PG_MAX_BYTES) throw TrackerError{LBA_E_LIMIT, "the pose graph's factor exceeds 6 GB of device memory"};
+    TR_HIP(hipSetDevice(t->cfg.device));
+    grow_bytes(t->d_arena, t->arena_cap, A.total, A.total + A.total / 2);
+    char* d = t->d_arena;
+    TR_HIP(hipMemcpyAsync(d, in.bytes.data(), up, hipMemcpyHostToDevice, t->stream));
+    TR_HIP(hipStreamSynchronize(t->stream));   // (the image is pageable and goes out of scope)
     auto ip = [&](size_t o) { return reinterpret_cast<const int*>(d + o); };
     auto dp = [&](size_t o) { return reinterpret_cast<double*>(d + o); };
     PgDev& D = R.D;
@@ -560,7 +538,7 @@ void pg_upload(lba_tracker* t, const lba_pg_vertex* v, const lba_pg_edge* e, int
     R.njobs = (int)G.jobs.size(); R.nlevel = G.nlevel; R.G = &G;
 }
 
-void pg_launch_check() { PG_HIP(hipGetLastError()); }
+void pg_launch_check() { TR_HIP(hipGetLastError()); }
 
 void pg_edges(const PgRun& R, const double* S, bool jac) {
     const dim3 g((unsigned)((R.D.ne + 63) / 64)), b(64);
@@ -571,7 +549,7 @@ void pg_edges(const PgRun& R, const double* S, bool jac) {
 
 void pg_assemble(const PgRun& R, double lambda) {
     hipStream_t s = R.t->stream;
-    PG_HIP(hipMemsetAsync(R.D.tiles, 0, (size_t)R.G->pl.ntile() * PG_TILE * sizeof(double), s));
+    TR_HIP(hipMemsetAsync(R.D.tiles, 0, (size_t)R.G->pl.ntile() * PG_TILE * sizeof(double), s));
     hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)R.njobs), dim3(64), 0, s, R.D, lambda);
     pg_launch_check();
 }
@@ -599,21 +577,12 @@ void pg_trial(const PgRun& R, double lambda, double* out3) {
     pg_edges(R, R.T, false);
     hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, s, R.D, lambda, 1);
     pg_launch_check();
-    PG_HIP(hipMemcpyAsync(out3, R.D.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    PG_HIP(hipStreamSynchronize(s));
+    TR_HIP(hipMemcpyAsync(out3, R.D.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    TR_HIP(hipStreamSynchronize(s));
 }
 
 double pg_ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
-}
-
-int pg_fail(lba_tracker* t, int what) {
-    if (what == 1) {
-        t->err = "the pose graph's factor exceeds 6 GB of device memory";
-        return LBA_E_LIMIT;
-    }
-    t->err = "HIP error";
-    return LBA_E_HIP;
 }
 
 void pg_unpack(const double* st, lba_pg_vertex& o) {
@@ -646,10 +615,8 @@ extern "C" int lba_posegraph_linearize(lba_tracker* t, const lba_pg_vertex* v, i
     PgHost G;
     const int rc = pg_plan(v, n_v, e, n_e, true, G);
     if (rc != LBA_OK) return rc;
-    if (H && G.na > PG_MAX_DENSE) {
-        t->err = "lba_posegraph_linearize: more than 2048 active free vertices for a dense H";
-        return LBA_E_LIMIT;
-    }
+    if (H && G.na > PG_MAX_DENSE)
+        return tracker_fail(t, {LBA_E_LIMIT, "lba_posegraph_linearize: more than 2048 active free vertices for a dense H"});
     const int ne = (int)G.eact.size(), nt = G.pl.ntile();
     std::vector<double> h_err((size_t)ne * 7), h_tiles((size_t)nt * PG_TILE), h_b((size_t)G.NP * PG_NB);
     try {
@@ -658,12 +625,12 @@ extern "C" int lba_posegraph_linearize(lba_tracker* t, const lba_pg_vertex* v, i
         pg_edges(R, R.S, true);
         pg_assemble(R, 0.0);
         hipStream_t s = t->stream;
-        PG_HIP(hipMemcpyAsync(h_err.data(), R.D.err, h_err.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        PG_HIP(hipMemcpyAsync(h_tiles.data(), R.D.tiles, h_tiles.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        PG_HIP(hipMemcpyAsync(h_b.data(), R.D.b, h_b.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        PG_HIP(hipStreamSynchronize(s));
-    } catch (int what) {
-        return pg_fail(t, what);
+        TR_HIP(hipMemcpyAsync(h_err.data(), R.D.err, h_err.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        TR_HIP(hipMemcpyAsync(h_tiles.data(), R.D.tiles, h_tiles.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        TR_HIP(hipMemcpyAsync(h_b.data(), R.D.b, h_b.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        TR_HIP(hipStreamSynchronize(s));
+    } catch (const TrackerError& err) {
+        return tracker_fail(t, err);
     }
     if (errors) {
         std::memset(errors, 0, (size_t)n_e * 7 * sizeof(double));
@@ -704,12 +671,12 @@ extern "C" int lba_posegraph_step(lba_tracker* t, const lba_pg_vertex* v, int32_
         pg_trial(R, lambda, out3);
         if (out3[2] == 0.0) {
             hipStream_t s = t->stream;
-            PG_HIP(hipMemcpyAsync(h_dx.data(), R.D.dxnat, h_dx.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            PG_HIP(hipMemcpyAsync(h_T.data(), R.T, h_T.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-            PG_HIP(hipStreamSynchronize(s));
+            TR_HIP(hipMemcpyAsync(h_dx.data(), R.D.dxnat, h_dx.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            TR_HIP(hipMemcpyAsync(h_T.data(), R.T, h_T.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+            TR_HIP(hipStreamSynchronize(s));
         }
-    } catch (int what) {
-        return pg_fail(t, what);
+    } catch (const TrackerError& err) {
+        return tracker_fail(t, err);
     }
     if (out3[2] != 0.0) return LBA_E_SOLVE;
     if (dx) std::memcpy(dx, h_dx.data(), h_dx.size() * sizeof(double));
@@ -735,7 +702,7 @@ extern "C" int lba_posegraph_optimize(lba_tracker* t, lba_pg_vertex* v, int32_t 
     st.panels = G.NP; st.tiles = G.pl.ntile(); st.fill_tiles = G.fill_tiles; st.levels = G.nlevel; st.chain = G.pl.chain;
     st.launches_per_solve = 1 + 2 * G.nlevel;
     std::vector<double> h_S((size_t)n_v * 8);
-    double lambda = 0.0;
+    LmCtl lm{0.0, 2.0, 0};
     int iters = 0;
     try {
         PgRun R;
@@ -743,90 +710,71 @@ extern "C" int lba_posegraph_optimize(lba_tracker* t, lba_pg_vertex* v, int32_t 
         const auto t2 = std::chrono::steady_clock::now();
         hipStream_t s = t->stream;
         const int max_trials = t->cfg.max_trials;
-        double ni = 2.0, out3[3];
-        int nbad = 0;
+        double out3[3];
         for (int k = 0; k < iterations; ++k) {
             // computeActiveErrors + activeRobustChi2 + buildSystem at the estimate
             pg_edges(R, R.S, true);
             hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, s, R.D, 0.0, 0);
             pg_launch_check();
-            PG_HIP(hipMemcpyAsync(out3, R.D.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-            PG_HIP(hipStreamSynchronize(s));
+            TR_HIP(hipMemcpyAsync(out3, R.D.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+            TR_HIP(hipStreamSynchronize(s));
             double currentChi = out3[0];
             const double iniChi = currentChi;
             if (k == 0) {
                 st.chi2_initial = currentChi;
-                if (lambda_init > 0) {
-                    lambda = lambda_init;
-                } else {   // computeLambdaInit: tau max|H_ii|
+                double lambda = lambda_init;
+                if (!(lambda_init > 0)) {   // computeLambdaInit: tau max|H_ii|
                     pg_assemble(R, 0.0);
                     std::vector<double> hd((size_t)G.NP * PG_NB);
-                    PG_HIP(hipMemcpyAsync(hd.data(), R.D.hdiag, hd.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-                    PG_HIP(hipStreamSynchronize(s));
+                    TR_HIP(hipMemcpyAsync(hd.data(), R.D.hdiag, hd.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+                    TR_HIP(hipStreamSynchronize(s));
                     double m = 0.0;
                     for (int sl = 0; sl < G.na; ++sl)
                         for (int d = 0; d < 7; ++d) m = std::max(m, std::fabs(hd[G.voff[G.slot_v[sl]] + d]));
                     lambda = t->cfg.tau * m;
                 }
-                ni = 2.0;
-                nbad = 0;
+                lm = LmCtl{lambda, 2.0, 0};
             }
             double rho = 0.0;
             int qmax = 0;
             do {
-                pg_solve(R, lambda);
-                pg_trial(R, lambda, out3);
+                pg_solve(R, lm.lambda);
+                pg_trial(R, lm.lambda, out3);
                 const bool ok = out3[2] == 0.0;
                 const double tempChi = ok ? out3[0] : DBL_MAX;
                 double scale = 1e-3;
                 if (ok) scale += out3[1];
                 else ++st.solve_failures;
                 ++st.trials;
-                rho = (currentChi - tempChi) / scale;
-                if (rho > 0 && std::isfinite(tempChi)) {
-                    const double w = 2 * rho - 1;
-                    double alpha = 1. - w * w * w;
-                    alpha = std::min(alpha, 2. / 3.);
-                    lambda *= std::max(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                    std::swap(R.S, R.T);
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                }
+                bool accept;
+                rho = lm_trial(lm, currentChi, tempChi, scale, accept);
+                if (accept) std::swap(R.S, R.T);
                 qmax++;
             } while (rho < 0 && qmax < max_trials);
             ++iters;
             st.chi2_final = currentChi;
             st.result = qmax == max_trials ? 1 : 0;
-            bool stop = qmax == max_trials || rho == 0;
-            if (!stop) {
-                if ((iniChi - currentChi) * 1e3 < iniChi) nbad++;
-                else nbad = 0;
-                stop = nbad >= 3;
-            }
-            if (stop && t->cfg.early_stop) break;
+            if (lm_stop(lm, iniChi, currentChi, rho, qmax, max_trials) && t->cfg.early_stop) break;
         }
         if (iterations == 0) {
             pg_edges(R, R.S, false);
             hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, s, R.D, 0.0, 0);
             pg_launch_check();
-            PG_HIP(hipMemcpyAsync(out3, R.D.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-            PG_HIP(hipStreamSynchronize(s));
+            TR_HIP(hipMemcpyAsync(out3, R.D.out, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+            TR_HIP(hipStreamSynchronize(s));
             st.chi2_initial = st.chi2_final = out3[0];
         }
-        PG_HIP(hipMemcpyAsync(h_S.data(), R.S, h_S.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-        PG_HIP(hipStreamSynchronize(s));
+        TR_HIP(hipMemcpyAsync(h_S.data(), R.S, h_S.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        TR_HIP(hipStreamSynchronize(s));
         const auto t3 = std::chrono::steady_clock::now();
         t->pg_ms[0] = pg_ms(t0, t1); t->pg_ms[1] = pg_ms(t1, t2); t->pg_ms[2] = pg_ms(t2, t3);
-    } catch (int what) {
-        return pg_fail(t, what);
+    } catch (const TrackerError& err) {
+        return tracker_fail(t, err);
     }
     for (int i = 0; i < n_v; ++i)
         if (G.slot[i] >= 0) pg_unpack(&h_S[(size_t)i * 8], v[i]);
     st.iterations = iters;
-    st.lambda_final = lambda;
+    st.lambda_final = lm.lambda;
     if (out) *out = st;
     return iters;
 }

@@ -20,6 +20,8 @@
 // as g2o inserts them.  Sums: per lane in row order, then an xor shuffle tree, then lane 0's value broadcast.
 // A failed factorisation (non-positive pivot) is a trial with chi2 = max whose state is the untouched one, k_track's
 // rule.  No atomics, no inter-workgroup traffic, no spin waits.  Latency-bound like k_track and k_vel_hyp.
+// The LM controller's state and rule and the 7 x 7 solve are lba_lm.hpp's (the rule is restated in lm_round, for the
+// reason given there), the arena and the error path lba_tracker.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +30,7 @@
 #include <cstring>
 
 #include "../../include/amc_lba.h"
+#include "lba_lm.hpp"
 #include "lba_math.hpp"
 #include "lba_tracker.hpp"
 
@@ -36,7 +39,6 @@ using namespace lba;
 namespace {
 
 constexpr int S3_WAVE = 64;
-constexpr int S3_CAMD = 16;        // Rcb(9) tcb(3) fx fy cx cy
 constexpr int S3_FIELDS = 12;      // Y1(3) Y2(3) z1(2) z2(2) w1 w2, then two int fields: cameras, dropped
 constexpr size_t S3_LDS_MAX = 64 * 1024;
 constexpr int S3_MIN_INLIERS = 10; // nCorrespondences - nBad < 10 returns 0 (src/Optimizer.cc:2328)
@@ -68,63 +70,14 @@ __device__ __forceinline__ int wave_sum(int x) {
     return x;
 }
 
-// (H + lambda I) x = b, H the packed upper triangle: Cholesky in registers, the same on every lane; 1 if positive
-__device__ __forceinline__ int solve7(const double* H, double lambda, const double* b, double* x) {
-    constexpr int N = 7;
-    double L[N][N];
-    int ok = 1;
-#pragma unroll
-    for (int i = 0, q = 0; i < N; ++i)
-#pragma unroll
-        for (int j = i; j < N; ++j, ++q) L[j][i] = H[q] + (i == j ? lambda : 0.0);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double d = L[k][k];
-#pragma unroll
-        for (int p = 0; p < k; ++p) d -= L[k][p] * L[k][p];
-        ok &= d > 0.0 ? 1 : 0;   // (a NaN pivot fails too; what follows it is never used)
-        const double r = sqrt(d);
-        L[k][k] = r;
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            double s = L[i][k];
-#pragma unroll
-            for (int p = 0; p < k; ++p) s -= L[i][p] * L[k][p];
-            L[i][k] = s / r;
-        }
-    }
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double s = b[i];
-#pragma unroll
-        for (int p = 0; p < i; ++p) s -= L[i][p] * y[p];
-        y[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int p = i + 1; p < N; ++p) s -= L[p][i] * x[p];
-        x[i] = s / L[i][i];
-    }
-    return ok;
-}
-
 struct S3Ctx {
-    const double* cam;   // LDS [2 n_cam][S3_CAMD]
+    const double* cam;   // LDS [2 n_cam][CAMD_N]
     const double* row;   // LDS [S3_FIELDS][stride]
     int* cams12;         // LDS [stride]: cam1 | cam2 << 16
     int* dropped;        // LDS [stride]
     int n, n_cam, stride, lane, fix_scale;
     double th2, delta;
 };
-
-__device__ __forceinline__ void load_camd(const double* c, CamD* d) {
-    for (int i = 0; i < 9; ++i) d->Rcb[i] = c[i];
-    for (int i = 0; i < 3; ++i) d->tcb[i] = c[9 + i];
-    d->fx = c[12]; d->fy = c[13]; d->cx = c[14]; d->cy = c[15];
-}
 
 // both edges of row i at the state S: errors, e^T Omega e and, if JAC, the Jacobians (2 x 7 each)
 template <bool JAC>
@@ -135,8 +88,8 @@ __device__ __forceinline__ void row_edges(const S3Ctx& C, const Sim3M& S, int i,
     for (int k = 0; k < S3_FIELDS; ++k) f[k] = C.row[k * C.stride + i];
     const int cc = C.cams12[i];
     CamD c1, c2;
-    load_camd(C.cam + (cc & 0xffff) * S3_CAMD, &c1);
-    load_camd(C.cam + (C.n_cam + (cc >> 16)) * S3_CAMD, &c2);
+    camd_load(C.cam + (cc & 0xffff) * CAMD_N, &c1);
+    camd_load(C.cam + (C.n_cam + (cc >> 16)) * CAMD_N, &c2);
     sim3_edge12(S, c1, f + 3, f + 6, C.fix_scale != 0, e12, JAC ? J12 : nullptr);
     sim3_edge21(S, c2, f, f + 8, C.fix_scale != 0, e21, JAC ? J21 : nullptr);
     w[0] = f[10]; w[1] = f[11];
@@ -167,11 +120,11 @@ __device__ __forceinline__ void accumulate(const double* J, const double* e, dou
     for (int a = 0; a < 7; ++a) b[a] += sw * (J[a] * e[0] + J[7 + a] * e[1]);
 }
 
-// optimize(iterations): g2o Levenberg (optimization_algorithm_levenberg.cpp:61-194), lambda from computeLambdaInit.
+// optimize(iterations): g2o Levenberg, lambda from computeLambdaInit.
 // S: the vertex; last: the state of the last computeActiveErrors (the last trial's, accepted or not).
 __device__ int lm_round(const S3Ctx& C, const S3Args& A, Sim3& S, Sim3& last, int iterations, bool robust) {
-    double lambda = 0.0, ni = 2.0;
-    int nbad = 0, iters = 0;
+    LmCtl lm{0.0, 2.0, 0};
+    int iters = 0;
     for (int k = 0; k < iterations; ++k) {
         double H[28], b[7], chi = 0.0;
 #pragma unroll
@@ -201,15 +154,13 @@ __device__ int lm_round(const S3Ctx& C, const S3Args& A, Sim3& S, Sim3& last, in
         if (k == 0) {
             double m = 0.0;
             for (int a = 0, q = 0; a < 7; q += 7 - a, ++a) m = fmax(m, fabs(H[q]));
-            lambda = A.tau * m;
-            ni = 2.0;
-            nbad = 0;
+            lm = LmCtl{A.tau * m, 2.0, 0};
         }
         double rho = 0.0;
         int qmax = 0;
         do {
             double x[7];
-            const int ok = solve7(H, lambda, b, x);
+            const int ok = chol_solve<7>(H, lm.lambda, b, x);
             Sim3 St = S;
             if (ok) {
                 if (C.fix_scale) x[6] = 0.0;   // oplusImpl (include/OptimizableTypes.h:162-163)
@@ -220,28 +171,31 @@ __device__ int lm_round(const S3Ctx& C, const S3Args& A, Sim3& S, Sim3& last, in
             if (!ok) tempChi = DBL_MAX;
             double scale = 1e-3;
             if (ok)
-                for (int i = 0; i < 7; ++i) scale += x[i] * (lambda * x[i] + b[i]);
+                for (int i = 0; i < 7; ++i) scale += x[i] * (lm.lambda * x[i] + b[i]);
+            // lm_trial and lm_stop (lba_lm.hpp), written out: called as functions they leave this arithmetic as it is
+            // but make the compiler round the other product of 2xy - 2wz in chi_at's rotation matrix, and S12 moves
+            // by 1e-11.  Keep the two in step with the header.
             rho = (currentChi - tempChi) / scale;
             if (rho > 0 && isfinite(tempChi)) {
                 const double t = 2 * rho - 1;
                 double alpha = 1. - t * t * t;
                 alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha);
-                ni = 2;
+                lm.lambda *= fmax(1. / 3., alpha);
+                lm.ni = 2;
                 currentChi = tempChi;
                 S = St;
             } else {
-                lambda *= ni;
-                ni *= 2;
+                lm.lambda *= lm.ni;
+                lm.ni *= 2;
             }
             qmax++;
         } while (rho < 0 && qmax < A.max_trials);
         ++iters;
         bool stop = qmax == A.max_trials || rho == 0;
         if (!stop) {
-            if ((iniChi - currentChi) * 1e3 < iniChi) nbad++;
-            else nbad = 0;
-            stop = nbad >= 3;
+            if ((iniChi - currentChi) * 1e3 < iniChi) lm.nbad++;
+            else lm.nbad = 0;
+            stop = lm.nbad >= 3;
         }
         if (stop && A.early_stop) break;
     }
@@ -268,7 +222,7 @@ __global__ __launch_bounds__(S3_WAVE) void k_sim3(S3Args A) {
     const int p = blockIdx.x, lane = threadIdx.x;
     const S3Pair P = A.pairs[p];
     double* sCam = s3_lds;
-    double* sRow = sCam + 2 * A.n_cam * S3_CAMD;
+    double* sRow = sCam + 2 * A.n_cam * CAMD_N;
     int* sInt = reinterpret_cast<int*>(sRow + (size_t)S3_FIELDS * A.stride);
     S3Ctx C;
     C.cam = sCam; C.row = sRow; C.cams12 = sInt; C.dropped = sInt + A.stride;
@@ -280,17 +234,14 @@ __global__ __launch_bounds__(S3_WAVE) void k_sim3(S3Args A) {
         const lba_sim3_cam& g = A.cams[P.cam0 + c];
         CamD d;
         sim3_cam_derive(g.q, g.t, g.fx, g.fy, g.cx, g.cy, &d);
-        double* o = sCam + c * S3_CAMD;
-        for (int i = 0; i < 9; ++i) o[i] = d.Rcb[i];
-        for (int i = 0; i < 3; ++i) o[9 + i] = d.tcb[i];
-        o[12] = d.fx; o[13] = d.fy; o[14] = d.cx; o[15] = d.cy;
+        camd_store(d, sCam + c * CAMD_N);
     }
     __syncthreads();
     for (int i = lane; i < P.n; i += S3_WAVE) {
         const lba_sim3_corr& r = A.corr[P.row0 + i];
         CamD c1, c2;
-        load_camd(sCam + r.cam1 * S3_CAMD, &c1);
-        load_camd(sCam + (A.n_cam + r.cam2) * S3_CAMD, &c2);
+        camd_load(sCam + r.cam1 * CAMD_N, &c1);
+        camd_load(sCam + (A.n_cam + r.cam2) * CAMD_N, &c2);
         double f[S3_FIELDS];
         sim3_body_point(c1, r.X1c, f);
         sim3_body_point(c2, r.X2c, f + 3);
@@ -330,12 +281,6 @@ __global__ __launch_bounds__(S3_WAVE) void k_sim3(S3Args A) {
     }
 }
 
-size_t reserve(size_t& total, size_t n_bytes) {
-    const size_t off = total;
-    total += (n_bytes + 7) & ~size_t(7);
-    return off;
-}
-
 }  // namespace
 
 extern "C" int lba_sim3_profile(lba_tracker* t, int32_t on, double* last_ms) {
@@ -365,37 +310,23 @@ extern "C" int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n
         stride = std::max(stride, (int)P.n_corr);
     }
     if (n_rows > 0x7fffffff) return LBA_E_ARG;
-    const size_t lds = sizeof(double) * (2 * (size_t)n_cam * S3_CAMD + (size_t)S3_FIELDS * stride) + sizeof(int) * 3 * (size_t)stride;
-    if (lds > S3_LDS_MAX) {
-        t->err = "a pair's correspondences and cameras exceed 64 KB of LDS";
-        return LBA_E_LIMIT;
-    }
+    const size_t lds = sizeof(double) * (2 * (size_t)n_cam * CAMD_N + (size_t)S3_FIELDS * stride) + sizeof(int) * 3 * (size_t)stride;
+    if (lds > S3_LDS_MAX) return tracker_fail(t, {LBA_E_LIMIT, "a pair's correspondences and cameras exceed 64 KB of LDS"});
     // ---- the arena: inputs (one upload), outputs (one download); its pinned host image has the same offsets
-    size_t total = 0;
-    const size_t o_pairs = reserve(total, (size_t)n_pairs * sizeof(S3Pair));
-    const size_t o_rows = reserve(total, n_rows * sizeof(lba_sim3_corr));
-    const size_t o_cams = reserve(total, (size_t)n_cam_rows * sizeof(lba_sim3_cam));
-    const size_t out0 = total;
-    const size_t o_state = reserve(total, (size_t)n_pairs * 8 * sizeof(double));
-    const size_t o_info = reserve(total, (size_t)n_pairs * 4 * sizeof(int));
-    const size_t o_flag = reserve(total, n_rows * sizeof(int));
+    ArenaLayout lay;
+    const size_t o_pairs = lay.take((size_t)n_pairs * sizeof(S3Pair));
+    const size_t o_rows = lay.take(n_rows * sizeof(lba_sim3_corr));
+    const size_t o_cams = lay.take((size_t)n_cam_rows * sizeof(lba_sim3_cam));
+    const size_t out0 = lay.total;
+    const size_t o_state = lay.take((size_t)n_pairs * 8 * sizeof(double));
+    const size_t o_info = lay.take((size_t)n_pairs * 4 * sizeof(int));
+    const size_t o_flag = lay.take(n_rows * sizeof(int));
+    const size_t total = lay.total;
     char* h = nullptr;
     try {
-        if (hipSetDevice(t->cfg.device) != hipSuccess) throw 0;
-        if (total > t->vel_cap || !t->d_vel) {
-            if (t->d_vel) (void)hipFree(t->d_vel);
-            t->d_vel = nullptr;
-            t->vel_cap = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&t->d_vel), total * 2) != hipSuccess) throw 0;
-            t->vel_cap = total * 2;
-        }
-        if (total > t->sim3_pin_cap || !t->h_sim3) {
-            if (t->h_sim3) (void)hipHostFree(t->h_sim3);
-            t->h_sim3 = nullptr;
-            t->sim3_pin_cap = 0;
-            if (hipHostMalloc(reinterpret_cast<void**>(&t->h_sim3), total * 2, hipHostMallocDefault) != hipSuccess) throw 0;
-            t->sim3_pin_cap = total * 2;
-        }
+        TR_HIP(hipSetDevice(t->cfg.device));
+        grow_bytes(t->d_arena, t->arena_cap, total, total * 2);
+        grow_bytes(t->h_sim3, t->sim3_pin_cap, total, total * 2, true);
         h = t->h_sim3;
         // per pair: its rows packed in pair order (overlapping ranges get rows of their own)
         S3Pair* sp = reinterpret_cast<S3Pair*>(h + o_pairs);
@@ -417,12 +348,11 @@ extern "C" int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n
             row0 += (size_t)P.n_corr;
         }
         std::memcpy(h + o_cams, cams, (size_t)n_cam_rows * sizeof(lba_sim3_cam));
-        char* d = t->d_vel;
+        char* d = t->d_arena;
         hipStream_t s = t->stream;
         if (t->sim3_timed && !t->sim3_ev[0])
-            for (hipEvent_t& e : t->sim3_ev)
-                if (hipEventCreate(&e) != hipSuccess) throw 0;
-        if (hipMemcpyAsync(d, h, out0, hipMemcpyHostToDevice, s) != hipSuccess) throw 0;
+            for (hipEvent_t& e : t->sim3_ev) TR_HIP(hipEventCreate(&e));
+        TR_HIP(hipMemcpyAsync(d, h, out0, hipMemcpyHostToDevice, s));
         S3Args a;
         a.pairs = reinterpret_cast<const S3Pair*>(d + o_pairs);
         a.corr = reinterpret_cast<const lba_sim3_corr*>(d + o_rows);
@@ -432,20 +362,19 @@ extern "C" int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n
         a.flag = reinterpret_cast<int*>(d + o_flag);
         a.tau = t->cfg.tau; a.max_trials = t->cfg.max_trials; a.early_stop = t->cfg.early_stop;
         a.n_cam = n_cam; a.stride = stride;
-        if (t->sim3_timed && hipEventRecord(t->sim3_ev[0], s) != hipSuccess) throw 0;
+        if (t->sim3_timed) TR_HIP(hipEventRecord(t->sim3_ev[0], s));
         hipLaunchKernelGGL(k_sim3, dim3((unsigned)n_pairs), dim3(S3_WAVE), lds, s, a);
-        if (hipGetLastError() != hipSuccess) throw 0;
-        if (t->sim3_timed && hipEventRecord(t->sim3_ev[1], s) != hipSuccess) throw 0;
-        if (hipMemcpyAsync(h + out0, d + out0, total - out0, hipMemcpyDeviceToHost, s) != hipSuccess) throw 0;
-        if (hipStreamSynchronize(s) != hipSuccess) throw 0;
+        TR_HIP(hipGetLastError());
+        if (t->sim3_timed) TR_HIP(hipEventRecord(t->sim3_ev[1], s));
+        TR_HIP(hipMemcpyAsync(h + out0, d + out0, total - out0, hipMemcpyDeviceToHost, s));
+        TR_HIP(hipStreamSynchronize(s));
         if (t->sim3_timed) {
             float ms = -1.f;
-            if (hipEventElapsedTime(&ms, t->sim3_ev[0], t->sim3_ev[1]) != hipSuccess) throw 0;
+            TR_HIP(hipEventElapsedTime(&ms, t->sim3_ev[0], t->sim3_ev[1]));
             t->sim3_ms = ms;
         }
-    } catch (int) {
-        t->err = "HIP error";
-        return LBA_E_HIP;
+    } catch (const TrackerError& e) {
+        return tracker_fail(t, e);
     }
     const S3Pair* sp = reinterpret_cast<const S3Pair*>(h + o_pairs);
     const double* r_state = reinterpret_cast<const double*>(h + o_state);

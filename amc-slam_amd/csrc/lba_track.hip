@@ -9,8 +9,8 @@
 // an asynchronous camera sees the GP pose between the two frames at that camera's time stamp, so the
 // frame has at most one sample per camera; J = J1 N with the sample's factor N (6 x 24), and
 // sum J^T W J = N^T (sum J1^T W J1) N per sample.  Edges, Jacobians and GP maths are the ones of
-// lba_math.hpp (src/G2oTypes.cc:162-223, include/G2oTypes.h:186-270); the LM loop is g2o's
-// OptimizationAlgorithmLevenberg (optimization_algorithm_levenberg.cpp:61-194) without a user lambda.
+// lba_math.hpp (src/G2oTypes.cc:162-223, include/G2oTypes.h:186-270); the LM loop is g2o's Levenberg controller of
+// lba_lm.hpp without a user lambda.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/amc_lba.h"
+#include "lba_lm.hpp"
 #include "lba_math.hpp"
 #include "lba_tracker.hpp"
 
@@ -29,7 +30,6 @@ using namespace lba;
 namespace {
 
 constexpr int TR_THREADS = 256;
-constexpr int CAMD_N = 16;    // Rcb(9) tcb(3) fx fy cx cy
 
 struct TrackArgs {
     lba_track_frame* frames;
@@ -45,12 +45,6 @@ struct TrackArgs {
     double huber_mono, huber_stereo, tau, lambda_init;
     int max_trials, early_stop;
 };
-
-__device__ __forceinline__ void load_camd(const double* c, CamD* d) {
-    for (int i = 0; i < 9; ++i) d->Rcb[i] = c[i];
-    for (int i = 0; i < 3; ++i) d->tcb[i] = c[9 + i];
-    d->fx = c[12]; d->fy = c[13]; d->cx = c[14]; d->cy = c[15];
-}
 
 __device__ __forceinline__ SE3 kf_se3(const double* k) {
     SE3 T;
@@ -127,7 +121,7 @@ __device__ __forceinline__ int residual(const TrackArgs& A, const TrackShared& S
                                         double* Xc, CamD& cd) {
     const lba_track_obs& ob = A.obs[o];
     const double* R = S.sR[A.obs_smp[o]];
-    load_camd(A.camd + (size_t)ob.cam * CAMD_N, &cd);
+    camd_load(A.camd + (size_t)ob.cam * CAMD_N, &cd);
     const double bf = S.ks[buf][1][14];
     if (ob.kind == LBA_STEREO) {
         project_residual<3>(R, R + 9, cd, ob.Xw, ob.z, bf, Xb, Xc, e);
@@ -393,52 +387,33 @@ __global__ __launch_bounds__(TR_THREADS) void k_track(TrackArgs A) {
     bool robust = true;
     for (int it = 0; it < 4; ++it) {
         // ---- initializeOptimization(0) + optimize(10): g2o Levenberg (lambda from computeLambdaInit)
-        double lambda = 0.0, ni = 2.0;
-        int nbad_lm = 0;
+        LmCtl lm{0.0, 2.0, 0};
         for (int k = 0; k < 10; ++k) {
             double currentChi = linearize(A, S, f, cur, robust, d0, s0, ns);
             const double iniChi = currentChi;
             if (k == 0) {
                 double m = 0.0;
                 for (int i = d0; i < 24; ++i) m = fmax(m, fabs(S.H[i * 24 + i]));
-                lambda = A.lambda_init > 0 ? A.lambda_init : A.tau * m;
-                ni = 2.0;
-                nbad_lm = 0;
+                lm = LmCtl{A.lambda_init > 0 ? A.lambda_init : A.tau * m, 2.0, 0};
             }
             double rho = 0.0;
             int qmax = 0;
             do {
-                const int ok = solve(S, lambda, d0);
+                const int ok = solve(S, lm.lambda, d0);
                 update(S, cur, cur ^ 1, d0, ok);
                 double tempChi = evaluate(A, S, f, cur ^ 1, robust, d0, s0, ns);
                 if (!ok) tempChi = DBL_MAX;
                 double scale = 1e-3;
                 if (ok)
-                    for (int i = 0; i < 24 - d0; ++i) scale += S.x[i] * (lambda * S.x[i] + S.bv[d0 + i]);
-                rho = (currentChi - tempChi) / scale;
-                if (rho > 0 && isfinite(tempChi)) {
-                    const double t = 2 * rho - 1;
-                    double alpha = 1. - t * t * t;
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                    cur ^= 1;   // discardTop: the trial state becomes current
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                }
+                    for (int i = 0; i < 24 - d0; ++i) scale += S.x[i] * (lm.lambda * S.x[i] + S.bv[d0 + i]);
+                bool accept;
+                rho = lm_trial(lm, currentChi, tempChi, scale, accept);
+                if (accept) cur ^= 1;   // discardTop: the trial state becomes current
                 qmax++;
                 __syncthreads();
             } while (rho < 0 && qmax < A.max_trials);
             ++iters;
-            bool stop = qmax == A.max_trials || rho == 0;
-            if (!stop) {
-                if ((iniChi - currentChi) * 1e3 < iniChi) nbad_lm++;
-                else nbad_lm = 0;
-                stop = nbad_lm >= 3;
-            }
-            if (stop && A.early_stop) break;
+            if (lm_stop(lm, iniChi, currentChi, rho, qmax, A.max_trials) && A.early_stop) break;
         }
         // ---- re-classification (Optimizer.cc:575-672) at the current estimate
         prep(A, S, cur, false, s0, ns);
@@ -482,26 +457,15 @@ __global__ __launch_bounds__(TR_THREADS) void k_track(TrackArgs A) {
     }
 }
 
-struct HipErr {
-    hipError_t e;
-};
-#define TCHK(x)                                    \
-    do {                                           \
-        hipError_t _e = (x);                       \
-        if (_e != hipSuccess) throw HipErr{_e};    \
-    } while (0)
-
-}  // namespace
-
-namespace {
 template <typename T>
 void grow(T*& p, size_t& cap, size_t n) {
     if (n <= cap && p) return;
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = std::max<size_t>(n, 1) * 2;
-    TCHK(hipMalloc(reinterpret_cast<void**>(&p), cap * sizeof(T)));
+    TR_HIP(hipMalloc(reinterpret_cast<void**>(&p), cap * sizeof(T)));
 }
+
 }  // namespace
 
 extern "C" {
@@ -527,11 +491,8 @@ void lba_tracker_destroy(lba_tracker* t) {
     if (!t) return;
     (void)hipSetDevice(t->cfg.device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
-    void* bufs[] = {t->d_frames, t->d_obs, t->d_obs_smp, t->d_smp0, t->d_smp_obs0, t->d_smp_kf, t->d_smp_t, t->d_camd, t->d_chi2, t->d_vel};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     if (t->stream) (void)hipStreamDestroy(t->stream);
-    delete t;
+    delete t;   // frees the buffers and the events
 }
 
 int lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_track_obs* obs, int32_t n_obs,
@@ -560,10 +521,7 @@ int lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_tra
         std::sort(ts.begin(), ts.end());
         ts.erase(std::unique(ts.begin(), ts.end()), ts.end());
         const int ns = (int)ts.size() + (has_kf ? 1 : 0);
-        if (ns > TR_MAXS) {
-            t->err = "more than 16 distinct observation times in a frame";
-            return LBA_E_LIMIT;
-        }
+        if (ns > TR_MAXS) return tracker_fail(t, {LBA_E_LIMIT, "more than 16 distinct observation times in a frame"});
         std::vector<std::vector<int>> by(ns);
         for (int i = F.obs0; i < F.obs0 + F.n_obs; ++i) {
             const lba_track_obs& o = obs[i];
@@ -592,21 +550,9 @@ int lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_tra
             for (int i = 0; i < frames[f].n_obs; ++i, ++q) sob[q] = obs[perm[q]];
         }
     }
-    std::vector<double> camd((size_t)n_cam * CAMD_N);
-    for (int c = 0; c < n_cam; ++c) {
-        Cam cm;
-        for (int i = 0; i < 4; ++i) cm.q[i] = cams[c].q[i];
-        for (int i = 0; i < 3; ++i) cm.t[i] = cams[c].t[i];
-        cm.fx = cams[c].fx; cm.fy = cams[c].fy; cm.cx = cams[c].cx; cm.cy = cams[c].cy;
-        CamD d;
-        cam_derive(cm, &d);
-        double* o = camd.data() + (size_t)c * CAMD_N;
-        for (int i = 0; i < 9; ++i) o[i] = d.Rcb[i];
-        for (int i = 0; i < 3; ++i) o[9 + i] = d.tcb[i];
-        o[12] = d.fx; o[13] = d.fy; o[14] = d.cx; o[15] = d.cy;
-    }
+    const std::vector<double> camd = camd_pack(cams, n_cam);
     try {
-        TCHK(hipSetDevice(t->cfg.device));
+        TR_HIP(hipSetDevice(t->cfg.device));
         grow(t->d_frames, t->cap[0], (size_t)n_frames);
         grow(t->d_obs, t->cap[1], perm.size());
         grow(t->d_obs_smp, t->cap[2], perm.size());
@@ -617,18 +563,18 @@ int lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_tra
         grow(t->d_smp_t, t->cap[7], smp_t.size());
         grow(t->d_camd, t->cap[8], camd.size());
         hipStream_t s = t->stream;
-        TCHK(hipMemcpyAsync(t->d_frames, sfr.data(), sizeof(lba_track_frame) * n_frames, hipMemcpyHostToDevice, s));
+        TR_HIP(hipMemcpyAsync(t->d_frames, sfr.data(), sizeof(lba_track_frame) * n_frames, hipMemcpyHostToDevice, s));
         if (!sob.empty()) {
-            TCHK(hipMemcpyAsync(t->d_obs, sob.data(), sizeof(lba_track_obs) * sob.size(), hipMemcpyHostToDevice, s));
-            TCHK(hipMemcpyAsync(t->d_obs_smp, obs_smp.data(), sizeof(int) * obs_smp.size(), hipMemcpyHostToDevice, s));
+            TR_HIP(hipMemcpyAsync(t->d_obs, sob.data(), sizeof(lba_track_obs) * sob.size(), hipMemcpyHostToDevice, s));
+            TR_HIP(hipMemcpyAsync(t->d_obs_smp, obs_smp.data(), sizeof(int) * obs_smp.size(), hipMemcpyHostToDevice, s));
         }
-        TCHK(hipMemcpyAsync(t->d_smp0, smp0.data(), sizeof(int) * smp0.size(), hipMemcpyHostToDevice, s));
-        TCHK(hipMemcpyAsync(t->d_smp_obs0, smp_obs0.data(), sizeof(int) * smp_obs0.size(), hipMemcpyHostToDevice, s));
+        TR_HIP(hipMemcpyAsync(t->d_smp0, smp0.data(), sizeof(int) * smp0.size(), hipMemcpyHostToDevice, s));
+        TR_HIP(hipMemcpyAsync(t->d_smp_obs0, smp_obs0.data(), sizeof(int) * smp_obs0.size(), hipMemcpyHostToDevice, s));
         if (!smp_kf.empty()) {
-            TCHK(hipMemcpyAsync(t->d_smp_kf, smp_kf.data(), sizeof(int) * smp_kf.size(), hipMemcpyHostToDevice, s));
-            TCHK(hipMemcpyAsync(t->d_smp_t, smp_t.data(), sizeof(double) * smp_t.size(), hipMemcpyHostToDevice, s));
+            TR_HIP(hipMemcpyAsync(t->d_smp_kf, smp_kf.data(), sizeof(int) * smp_kf.size(), hipMemcpyHostToDevice, s));
+            TR_HIP(hipMemcpyAsync(t->d_smp_t, smp_t.data(), sizeof(double) * smp_t.size(), hipMemcpyHostToDevice, s));
         }
-        TCHK(hipMemcpyAsync(t->d_camd, camd.data(), sizeof(double) * camd.size(), hipMemcpyHostToDevice, s));
+        TR_HIP(hipMemcpyAsync(t->d_camd, camd.data(), sizeof(double) * camd.size(), hipMemcpyHostToDevice, s));
         TrackArgs a;
         a.frames = t->d_frames; a.obs = t->d_obs; a.obs_smp = t->d_obs_smp; a.smp0 = t->d_smp0;
         a.smp_obs0 = t->d_smp_obs0; a.smp_t = t->d_smp_t; a.smp_kf = t->d_smp_kf; a.camd = t->d_camd; a.chi2 = t->d_chi2;
@@ -661,14 +607,13 @@ int lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_tra
         a.tau = t->cfg.tau; a.lambda_init = t->cfg.lambda_init;
         a.max_trials = t->cfg.max_trials; a.early_stop = t->cfg.early_stop;
         hipLaunchKernelGGL(k_track, dim3(n_frames), dim3(TR_THREADS), 0, s, a);
-        TCHK(hipGetLastError());
-        TCHK(hipMemcpyAsync(sfr.data(), t->d_frames, sizeof(lba_track_frame) * n_frames, hipMemcpyDeviceToHost, s));
+        TR_HIP(hipGetLastError());
+        TR_HIP(hipMemcpyAsync(sfr.data(), t->d_frames, sizeof(lba_track_frame) * n_frames, hipMemcpyDeviceToHost, s));
         if (!sob.empty())
-            TCHK(hipMemcpyAsync(sob.data(), t->d_obs, sizeof(lba_track_obs) * sob.size(), hipMemcpyDeviceToHost, s));
-        TCHK(hipStreamSynchronize(s));
-    } catch (const HipErr&) {
-        t->err = "HIP error";
-        return LBA_E_HIP;
+            TR_HIP(hipMemcpyAsync(sob.data(), t->d_obs, sizeof(lba_track_obs) * sob.size(), hipMemcpyDeviceToHost, s));
+        TR_HIP(hipStreamSynchronize(s));
+    } catch (const TrackerError& e) {
+        return tracker_fail(t, e);
     }
     for (size_t q = 0; q < perm.size(); ++q) obs[perm[q]].outlier = sob[q].outlier;
     for (int f = 0; f < n_frames; ++f) {

@@ -1,7 +1,8 @@
 // lba_track_vel.hip — the hypotheses of Tracking::MCRansac (src/Tracking.cc:1939-2002) on the GPU: one
 // Optimizer::OptimizeVel (src/Optimizer.cc:2364-2447) per sampled triple, the step before lba_track.
 //
-// A hypothesis is a 6-dof velocity fitted to three EdgeVelReproj edges by optimize(40) of g2o's Levenberg and then
+// A hypothesis is a 6-dof velocity fitted to three EdgeVelReproj edges by optimize(40) of g2o's Levenberg (the
+// controller and the 6 x 6 solve of lba_lm.hpp, the arena of lba_tracker.hpp: DESIGN.md §7 item 8) and then
 // scored on every matched feature of the frame.  Hypotheses are independent and each is a short dependent chain on
 // a 6 x 6 system, so k_vel_hyp gives ONE WAVE to each hypothesis of the batch: lanes 0..2 hold the three edges
 // (error, Jacobian, Huber weight), H and b are their sums broadcast in the edges' order, and every lane carries the
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "../../include/amc_lba.h"
+#include "lba_lm.hpp"
 #include "lba_math.hpp"
 #include "lba_tracker.hpp"
 
@@ -30,7 +32,6 @@ using namespace lba;
 namespace {
 
 constexpr int VEL_WAVE = 64;
-constexpr int CAMD_N = 16;   // Rcb(9) tcb(3) fx fy cx cy
 
 struct VelFrame {
     double q[4], t[3], vel[6];
@@ -61,12 +62,6 @@ struct VelArgs {
     int iterations, max_trials, early_stop;
 };
 
-__device__ __forceinline__ void load_camd(const double* c, CamD* d) {
-    for (int i = 0; i < 9; ++i) d->Rcb[i] = c[i];
-    for (int i = 0; i < 3; ++i) d->tcb[i] = c[9 + i];
-    d->fx = c[12]; d->fy = c[13]; d->cx = c[14]; d->cy = c[15];
-}
-
 // T^-1 of the last frame's pose (Sophus cast<double>(): normalised quaternion)
 __device__ __forceinline__ SE3 frame_inverse(const VelFrame& F) {
     SE3 T;
@@ -93,48 +88,6 @@ __device__ __forceinline__ double sum3(double x) {
     return (__shfl(x, 0) + __shfl(x, 1)) + __shfl(x, 2);
 }
 
-// (H + lambda I) x = b, H the packed upper triangle: Cholesky in registers, the same on every lane; 1 if positive
-__device__ __forceinline__ int solve6(const double* H, double lambda, const double* b, double* x) {
-    double L[6][6];
-    int ok = 1;
-#pragma unroll
-    for (int i = 0, q = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j, ++q) L[j][i] = H[q] + (i == j ? lambda : 0.0);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double d = L[k][k];
-#pragma unroll
-        for (int p = 0; p < k; ++p) d -= L[k][p] * L[k][p];
-        ok &= d > 0.0 ? 1 : 0;   // (a NaN pivot fails too; what follows it is never used)
-        const double r = sqrt(d);
-        L[k][k] = r;
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) {
-            double s = L[i][k];
-#pragma unroll
-            for (int p = 0; p < k; ++p) s -= L[i][p] * L[k][p];
-            L[i][k] = s / r;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-#pragma unroll
-        for (int p = 0; p < i; ++p) s -= L[i][p] * y[p];
-        y[i] = s / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int p = i + 1; p < 6; ++p) s -= L[p][i] * x[p];
-        x[i] = s / L[i][i];
-    }
-    return ok;
-}
-
 __global__ __launch_bounds__(VEL_WAVE) void k_vel_hyp(VelArgs A) {
     __shared__ double sM[TR_MAXS][12];   // exp(v dt) per (cam, dt): Rp(9) tp(3)
     const int w = blockIdx.x, lane = threadIdx.x;
@@ -145,16 +98,15 @@ __global__ __launch_bounds__(VEL_WAVE) void k_vel_hyp(VelArgs A) {
     const lba_vel_obs eob = A.obs[eo];
     const int es = A.obs_smp[eo];
     CamD ecd;
-    load_camd(A.camd + (size_t)eob.cam * CAMD_N, &ecd);
+    camd_load(A.camd + (size_t)eob.cam * CAMD_N, &ecd);
     double eXb[3];
     body_point(Ti, eob.Xw, eXb);
 
     double v[6];
     for (int i = 0; i < 6; ++i) v[i] = F.vel[i];
-    // ---- optimize(iterations): g2o Levenberg (optimization_algorithm_levenberg.cpp:61-194), lambda from
-    //      computeLambdaInit, on the three level-0 edges
-    double lambda = 0.0, ni = 2.0;
-    int nbad = 0, iters = 0;
+    // ---- optimize(iterations): g2o Levenberg, lambda from computeLambdaInit, on the three level-0 edges
+    LmCtl lm{0.0, 2.0, 0};
+    int iters = 0;
     for (int k = 0; k < A.iterations; ++k) {
         motions(A, F, v, sM);
         double e[2], Xc[3], J[12], H[21], b[6], r0, r1;
@@ -173,15 +125,13 @@ __global__ __launch_bounds__(VEL_WAVE) void k_vel_hyp(VelArgs A) {
         if (k == 0) {
             double m = 0.0;
             for (int a = 0, q = 0; a < 6; q += 6 - a, ++a) m = fmax(m, fabs(H[q]));
-            lambda = A.tau * m;
-            ni = 2.0;
-            nbad = 0;
+            lm = LmCtl{A.tau * m, 2.0, 0};
         }
         double rho = 0.0;
         int qmax = 0;
         do {
             double x[6], vt[6];
-            const int ok = solve6(H, lambda, b, x);
+            const int ok = chol_solve<6>(H, lm.lambda, b, x);
             for (int i = 0; i < 6; ++i) vt[i] = ok ? v[i] + x[i] : v[i];
             motions(A, F, vt, sM);
             vel_reproj_error(sM[es], sM[es] + 9, ecd, eXb, eob.z, Xc, e);
@@ -190,30 +140,15 @@ __global__ __launch_bounds__(VEL_WAVE) void k_vel_hyp(VelArgs A) {
             if (!ok) tempChi = DBL_MAX;
             double scale = 1e-3;
             if (ok)
-                for (int i = 0; i < 6; ++i) scale += x[i] * (lambda * x[i] + b[i]);
-            rho = (currentChi - tempChi) / scale;
-            if (rho > 0 && isfinite(tempChi)) {
-                const double t = 2 * rho - 1;
-                double alpha = 1. - t * t * t;
-                alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha);
-                ni = 2;
-                currentChi = tempChi;
+                for (int i = 0; i < 6; ++i) scale += x[i] * (lm.lambda * x[i] + b[i]);
+            bool accept;
+            rho = lm_trial(lm, currentChi, tempChi, scale, accept);
+            if (accept)
                 for (int i = 0; i < 6; ++i) v[i] = vt[i];
-            } else {
-                lambda *= ni;
-                ni *= 2;
-            }
             qmax++;
         } while (rho < 0 && qmax < A.max_trials);
         ++iters;
-        bool stop = qmax == A.max_trials || rho == 0;
-        if (!stop) {
-            if ((iniChi - currentChi) * 1e3 < iniChi) nbad++;
-            else nbad = 0;
-            stop = nbad >= 3;
-        }
-        if (stop && A.early_stop) break;
+        if (lm_stop(lm, iniChi, currentChi, rho, qmax, A.max_trials) && A.early_stop) break;
     }
     // ---- computeError() on every edge of the frame: inlier iff ||e|| <= threshold (Optimizer.cc:2425-2440)
     motions(A, F, v, sM);
@@ -226,7 +161,7 @@ __global__ __launch_bounds__(VEL_WAVE) void k_vel_hyp(VelArgs A) {
             const lba_vel_obs& ob = A.obs[F.obs0 + i];
             const int s = A.obs_smp[F.obs0 + i];
             CamD cd;
-            load_camd(A.camd + (size_t)ob.cam * CAMD_N, &cd);
+            camd_load(A.camd + (size_t)ob.cam * CAMD_N, &cd);
             double Xb[3], Xc[3], e[2];
             body_point(Ti, ob.Xw, Xb);
             vel_reproj_error(sM[s], sM[s] + 9, cd, Xb, ob.z, Xc, e);
@@ -262,26 +197,6 @@ __global__ __launch_bounds__(VEL_WAVE) void k_vel_select(VelArgs A) {
     }
 }
 
-// host image of the arena: sections at 8-byte offsets
-struct Arena {
-    std::vector<char> bytes;
-    template <typename T>
-    size_t put(const T* p, size_t count) {
-        const size_t off = bytes.size(), n = count * sizeof(T);
-        bytes.resize(off + ((n + 7) & ~size_t(7)));
-        if (n) std::memcpy(bytes.data() + off, p, n);
-        return off;
-    }
-    template <typename T>
-    size_t put(const std::vector<T>& v) { return put(v.data(), v.size()); }
-};
-
-size_t reserve(size_t& total, size_t n_bytes) {
-    const size_t off = total;
-    total += (n_bytes + 7) & ~size_t(7);
-    return off;
-}
-
 }  // namespace
 
 extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32_t n_frames, lba_vel_obs* obs, int32_t n_obs,
@@ -315,10 +230,7 @@ extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32
             if (ncd == TR_MAXS) over = true;
             else cd[ncd++] = key;
         }
-        if (over) {
-            t->err = "more than 16 distinct (camera, dt) pairs in a frame";
-            return LBA_E_LIMIT;
-        }
+        if (over) return tracker_fail(t, {LBA_E_LIMIT, "more than 16 distinct (camera, dt) pairs in a frame"});
         std::sort(cd, cd + ncd);
         for (int i = F.obs0; i < F.obs0 + F.n_obs; ++i)
             obs_smp[i] = (int)(std::find(cd, cd + ncd, std::make_pair((int)obs[i].cam, obs[i].dt)) - cd);
@@ -348,48 +260,29 @@ extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32
         words += (long long)F.n_hyp * V.words;
     }
     const size_t n_work = work_frame.size();
-    std::vector<double> camd((size_t)n_cam * CAMD_N);
-    for (int c = 0; c < n_cam; ++c) {
-        Cam cm;
-        for (int i = 0; i < 4; ++i) cm.q[i] = cams[c].q[i];
-        for (int i = 0; i < 3; ++i) cm.t[i] = cams[c].t[i];
-        cm.fx = cams[c].fx; cm.fy = cams[c].fy; cm.cx = cams[c].cx; cm.cy = cams[c].cy;
-        CamD d;
-        cam_derive(cm, &d);
-        double* o = camd.data() + (size_t)c * CAMD_N;
-        for (int i = 0; i < 9; ++i) o[i] = d.Rcb[i];
-        for (int i = 0; i < 3; ++i) o[9 + i] = d.tcb[i];
-        o[12] = d.fx; o[13] = d.fy; o[14] = d.cx; o[15] = d.cy;
-    }
     // ---- the arena: inputs (one upload), outputs (one download), masks (device only)
-    Arena in;
+    ArenaImage in;
     const size_t o_frames = in.put(vf);
     const size_t o_obs = in.put(obs, (size_t)n_obs);
     const size_t o_obs_smp = in.put(obs_smp), o_smp_dt = in.put(smp_dt), o_tri = in.put(tri);
-    const size_t o_work = in.put(work_frame), o_camd = in.put(camd);
-    size_t total = in.bytes.size();
-    const size_t out0 = total;
-    const size_t o_hvel = reserve(total, n_work * 6 * sizeof(double));
-    const size_t o_fvel = reserve(total, (size_t)n_frames * 6 * sizeof(double));
-    const size_t o_hinl = reserve(total, n_work * sizeof(int));
-    const size_t o_hit = reserve(total, n_work * sizeof(int));
-    const size_t o_best = reserve(total, (size_t)n_frames * 2 * sizeof(int));
-    const size_t o_inl = reserve(total, (size_t)rows * sizeof(int));
-    const size_t out1 = total;
-    const size_t o_mask = reserve(total, (size_t)words * sizeof(unsigned long long));
+    const size_t o_work = in.put(work_frame), o_camd = in.put(camd_pack(cams, n_cam));
+    ArenaLayout& lay = in.lay;
+    const size_t out0 = lay.total;
+    const size_t o_hvel = lay.take(n_work * 6 * sizeof(double));
+    const size_t o_fvel = lay.take((size_t)n_frames * 6 * sizeof(double));
+    const size_t o_hinl = lay.take(n_work * sizeof(int));
+    const size_t o_hit = lay.take(n_work * sizeof(int));
+    const size_t o_best = lay.take((size_t)n_frames * 2 * sizeof(int));
+    const size_t o_inl = lay.take((size_t)rows * sizeof(int));
+    const size_t out1 = lay.total;
+    const size_t o_mask = lay.take((size_t)words * sizeof(unsigned long long));
     std::vector<char> out(out1 - out0);
     try {
-        if (hipSetDevice(t->cfg.device) != hipSuccess) throw 0;
-        if (total > t->vel_cap || !t->d_vel) {
-            if (t->d_vel) (void)hipFree(t->d_vel);
-            t->d_vel = nullptr;
-            t->vel_cap = 0;
-            if (hipMalloc(reinterpret_cast<void**>(&t->d_vel), total * 2) != hipSuccess) throw 0;
-            t->vel_cap = total * 2;
-        }
-        char* d = t->d_vel;
+        TR_HIP(hipSetDevice(t->cfg.device));
+        grow_bytes(t->d_arena, t->arena_cap, lay.total, lay.total * 2);
+        char* d = t->d_arena;
         hipStream_t s = t->stream;
-        if (hipMemcpyAsync(d, in.bytes.data(), in.bytes.size(), hipMemcpyHostToDevice, s) != hipSuccess) throw 0;
+        TR_HIP(hipMemcpyAsync(d, in.bytes.data(), in.bytes.size(), hipMemcpyHostToDevice, s));
         VelArgs a;
         a.frames = reinterpret_cast<const VelFrame*>(d + o_frames);
         a.obs = reinterpret_cast<const lba_vel_obs*>(d + o_obs);
@@ -409,12 +302,11 @@ extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32
         a.iterations = P.iterations; a.max_trials = t->cfg.max_trials; a.early_stop = t->cfg.early_stop;
         if (n_work) hipLaunchKernelGGL(k_vel_hyp, dim3((unsigned)n_work), dim3(VEL_WAVE), 0, s, a);
         hipLaunchKernelGGL(k_vel_select, dim3(n_frames), dim3(VEL_WAVE), 0, s, a);
-        if (hipGetLastError() != hipSuccess) throw 0;
-        if (hipMemcpyAsync(out.data(), d + out0, out.size(), hipMemcpyDeviceToHost, s) != hipSuccess) throw 0;
-        if (hipStreamSynchronize(s) != hipSuccess) throw 0;
-    } catch (int) {
-        t->err = "HIP error";
-        return LBA_E_HIP;
+        TR_HIP(hipGetLastError());
+        TR_HIP(hipMemcpyAsync(out.data(), d + out0, out.size(), hipMemcpyDeviceToHost, s));
+        TR_HIP(hipStreamSynchronize(s));
+    } catch (const TrackerError& e) {
+        return tracker_fail(t, e);
     }
     const double* r_hvel = reinterpret_cast<const double*>(out.data() + (o_hvel - out0));
     const double* r_fvel = reinterpret_cast<const double*>(out.data() + (o_fvel - out0));

@@ -11,7 +11,6 @@ mkdir -p "$TMP/amc-slam_amd" "$ROOT/amc-slam_amd/lib/exp"
 cp -r "$ROOT/amc-slam_amd/csrc" "$TMP/amc-slam_amd/csrc"
 cp -r "$ROOT/include" "$TMP/include"
 python3 "$PATCH" "$TMP/amc-slam_amd/csrc"
-C=$TMP/amc-slam_amd/csrc
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" "$C/lba_kernels.hip" "$C/lba_host.hip" \
-    "$C/lba_track.hip" "$C/lba_debug.hip" -o "$ROOT/amc-slam_amd/lib/exp/$NAME.so" -lrccl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared "$@" "$TMP"/amc-slam_amd/csrc/lba_*.hip \
+    -o "$ROOT/amc-slam_amd/lib/exp/$NAME.so" -lrccl
 echo "built $ROOT/amc-slam_amd/lib/exp/$NAME.so"
