@@ -33,8 +33,10 @@
 #include "lba_device.hpp"
 #include "lba_plan.hpp"
 #include "lba_math.hpp"
+#include "lba_setup.hpp"
 
 using namespace lba;
+using namespace lba_setup;
 
 // the last panel pattern an engine planned (plan_panels_cached)
 struct PlanCache {
@@ -100,10 +102,7 @@ struct lba_problem {
     std::vector<size_t> up_end;             // bytes staged in each chunk this set-up (the current one: up_off)
     size_t up_chunk = 0, up_off = 0;        // allocation position
     size_t up_fchunk = 0, up_foff = 0;      // flushed up to here
-    // observation-sized host scratch arrays of set_problem, kept between calls: resizing to the same
-    // length touches nothing (no allocation, page faults or zeroing per window; every element is written)
-    std::vector<int> scr_i[16];
-    std::vector<double> scr_d[2];
+    SetupScratch scr;             // observation-sized host arrays of set_problem's stages, kept between calls
     // device ranges set_problem zeroes: collected, then cleared by ONE kernel launch at its end (k_zero_ranges)
     // instead of one hipMemsetAsync each (~17 runtime calls and ~28 fill kernels per set-up)
     std::vector<unsigned long long> zero_list;   // pairs: device address, 4-byte words
@@ -162,11 +161,6 @@ struct HipError {
         hipError_t _e = (x);                        \
         if (_e != hipSuccess) throw HipError{_e, #x}; \
     } while (0)
-
-struct ApiError {
-    int code;
-    std::string msg;
-};
 
 // the caller's all-reduce (sum, in place, enqueued on the problem's stream)
 void preduce(lba_problem* p, double* buf, int64_t n) {
@@ -388,140 +382,6 @@ T* dupload(lba_problem* p, const std::vector<T>& v) {
     return d;
 }
 
-// f(i) for i in [0, n) on up to SETUP_THREADS_MAX (16) host threads, at most the CPUs this process may run on
-// (LBA_SETUP_THREADS overrides; 1: serial).  Round 3 measured 16 threads no faster than 8
-// (profiles/r3ai_setup_threads.txt); round 4's parallel tile-list concatenation and device-order records made
-// the 16-piece passes scale, and 16 is the default since (profiles/r4z_setup_phases.txt).  Callers split work into a fixed number of pieces, so the
-// results never depend on the thread count.  The workers persist (a set-up makes a dozen parallel passes;
-// spawning threads per pass cost ~0.1 ms each) and, after a pass, poll for the next one for a while before
-// they sleep: a set-up's passes follow each other within a millisecond, and an OS wake-up of the workers per
-// pass cost more than many of the passes themselves.  Pieces are claimed from one counter that packs
-// (pass, piece), so a worker that arrives late takes no piece of a later pass for an earlier one; the caller
-// waits for the pieces to be finished, not for every worker to have looked in.  A pass that finds the pool
-// busy (another problem setting up on another thread) runs on its caller's thread alone.
-constexpr int SETUP_THREADS_MAX = 16;
-// the fixed number of pieces every parallel pass of the set-up splits its work into (the results do not depend on
-// the thread count; tiles never straddle a piece boundary)
-constexpr int SETUP_PIECES = 16;
-class SetupPool {
-  public:
-    static SetupPool& get() {
-        static SetupPool pool;
-        return pool;
-    }
-    int size() const { return (int)workers_.size() + 1; }
-    // false: the pool is in use (the caller runs the pass itself)
-    template <class F>
-    bool run(int n, F& f) {
-        std::unique_lock<std::mutex> busy(busy_, std::try_to_lock);
-        if (!busy.owns_lock()) return false;
-        std::function<void(int)> job = [&](int i) { f(i); };
-        job_ = &job;
-        n_.store(n, std::memory_order_relaxed);
-        done_.store(0, std::memory_order_relaxed);
-        err_ = nullptr;
-        const unsigned long long g = ++pass_;
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            claim_.store(g << 32, std::memory_order_release);   // publishes job_ / n_ with the pass number
-        }
-        cv_.notify_all();
-        work(g);   // the caller takes pieces too
-        for (int spins = 0; done_.load(std::memory_order_acquire) < n; ++spins)
-            if (spins > 4096) std::this_thread::yield();
-        // close the pass before any field of the next one is written: a worker that loaded this pass's
-        // last claim word (every piece taken) and was preempted before its bound check would otherwise
-        // pass that check against the next pass's larger n_ and win its CAS against the unchanged word,
-        // running a piece of the next job ahead of its publication
-        claim_.store((g << 32) | CLOSED, std::memory_order_release);
-        job_ = nullptr;
-        if (err_) std::rethrow_exception(err_);
-        return true;
-    }
-
-  private:
-    static constexpr int POLL_US = 3000;   // how long an idle worker polls for the next pass before it sleeps
-    static constexpr unsigned long long CLOSED = 0x7fffffffull;   // piece word of a finished pass (>= any n)
-    SetupPool() {
-        const char* e = std::getenv("LBA_SETUP_THREADS");
-        const int v = e ? std::atoi(e) : 0;
-        int avail = (int)std::thread::hardware_concurrency();
-        cpu_set_t cs;
-        if (sched_getaffinity(0, sizeof(cs), &cs) == 0) avail = std::min(avail > 0 ? avail : CPU_COUNT(&cs), CPU_COUNT(&cs));
-        const int nt = v > 0 ? v : std::max(1, std::min(SETUP_THREADS_MAX, avail));
-        for (int t = 1; t < nt; ++t)
-            workers_.emplace_back([this] {
-                unsigned long long seen = 0;
-                while (true) {
-                    auto fresh = [&] { return stop_.load(std::memory_order_acquire) ||
-                                              (claim_.load(std::memory_order_acquire) >> 32) != seen; };
-                    const auto t0 = std::chrono::steady_clock::now();
-                    while (!fresh()) {
-                        for (int k = 0; k < 64 && !fresh(); ++k) __builtin_ia32_pause();
-                        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(POLL_US)) {
-                            std::unique_lock<std::mutex> lk(m_);
-                            cv_.wait(lk, fresh);
-                        }
-                    }
-                    if (stop_.load(std::memory_order_acquire)) return;
-                    seen = claim_.load(std::memory_order_acquire) >> 32;
-                    work(seen);
-                }
-            });
-    }
-    ~SetupPool() {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            stop_.store(true, std::memory_order_release);
-        }
-        cv_.notify_all();
-        for (auto& w : workers_) w.join();
-    }
-    // claim pieces of pass g until none is left (or the pass is over); every piece claimed is counted done
-    void work(unsigned long long g) {
-        for (;;) {
-            unsigned long long c = claim_.load(std::memory_order_acquire);
-            int i;
-            do {
-                if ((c >> 32) != g || (int)(c & 0xffffffffu) >= n_.load(std::memory_order_relaxed)) return;
-                i = (int)(c & 0xffffffffu);
-            } while (!claim_.compare_exchange_weak(c, c + 1, std::memory_order_acq_rel, std::memory_order_acquire));
-            try {
-                (*job_)(i);
-            } catch (...) {
-                std::lock_guard<std::mutex> lk(m_);
-                if (!err_) err_ = std::current_exception();
-            }
-            done_.fetch_add(1, std::memory_order_acq_rel);
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex busy_, m_;
-    std::condition_variable cv_;
-    std::function<void(int)>* job_ = nullptr;
-    std::atomic<int> n_{0};
-    unsigned long long pass_ = 0;
-    std::atomic<unsigned long long> claim_{0};   // pass << 32 | next piece
-    std::atomic<int> done_{0};
-    std::atomic<bool> stop_{false};
-    std::exception_ptr err_;
-};
-
-template <class F>
-void par_for(int n, F f) {
-    SetupPool& pool = SetupPool::get();
-    if (n <= 1 || pool.size() <= 1 || !pool.run(n, f))
-        for (int i = 0; i < n; ++i) f(i);
-}
-
-inline bool is_gp(int kind) { return kind == LBA_MONO_GP || kind == LBA_STEREO_GP; }
-inline int obs_dim(int kind) { return (kind == LBA_STEREO_GP || kind == LBA_STEREO) ? 3 : 2; }
-
-void normalize_q(const double* q, double* o) {
-    const Quat n = qnormalize(Quat{q[0], q[1], q[2], q[3]});
-    o[0] = n.x; o[1] = n.y; o[2] = n.z; o[3] = n.w;
-}
-
 // 6x6 inverse (Gauss-Jordan, partial pivoting) for GaussianProcess::mQcInv = Qc.inverse()
 bool inverse6(const double* A, double* R) {
     double M[6][12];
@@ -556,1033 +416,106 @@ void zero_later(lba_problem* p, void* d, size_t bytes) {
 }
 void flush_zero_ranges(lba_problem* p);
 
-inline int ublock_id(int n_pb, int bi, int bj) { return bi * n_pb - bi * (bi - 1) / 2 + (bj - bi); }
-
 // ------------------------------------------------------------------------------------------------
-// scratch array k of set_problem, n elements (contents unspecified: the caller writes every element)
-std::vector<int>& scr_int(lba_problem* p, int k, size_t n) {
-    p->scr_i[k].resize(n);
-    return p->scr_i[k];
+// set_problem: the host stages of lba_setup.hpp, then the device half below.  The order of the dalloc calls and of
+// the dupload / upload_into / zero_later calls is part of the layout: allocs are reused by position from window
+// to window, and flush_uploads sends what was staged since the last phase boundary.
+
+// k_lin_schur's packed inputs (lba_device.hpp): the tile descriptors in dispatch order and one record per
+// observation
+void pack_dispatch(const Tiles& T, const SetupScratch& scr, int n_obs, std::vector<TileDesc>& desc,
+                   std::vector<ObsRec>& rec) {
+    const TileLists& l = T.l;
+    const int n_tiles = T.n_tiles(), n_stiles = T.n_stiles;
+    const std::vector<int>&ob_meta = scr.ob_meta, &ob_kfa = scr.ob_kfa, &ob_kfb = scr.ob_kfb, &ob_smp = scr.ob_smp,
+                    &ob_lm = scr.ob_lm, &ob_row = scr.ob_row, &pair_r0 = scr.pair_r0, &lm_r0 = scr.lm_r0;
+    const std::vector<double>&ob_z = scr.ob_z, &ob_w = scr.ob_w;
+    // k_lin_schur's workgroup -> tile order: longest first by a cost estimate (list scheduling: the tiles
+    // outnumber the resident workgroup slots, ~1.4x at config 1, and the costly tiles, many KFs and Schur
+    // entries, sit at the end of the landmark order, so in index order the last round of workgroups ran
+    // long after most CUs were idle).  Cost: a non-negative least-squares fit of measured tile durations
+    // on the tile shape (us ~ 0.027 npair + 0.775 nlm + 0.077 nsent + 1.807 nkf, profiles/r3aq_tile_order.txt)
+    std::vector<long long> cost(n_tiles);
+    std::vector<int> perm(n_tiles);
+    for (int t = 0; t < n_tiles; ++t) {
+        cost[t] = 27LL * l.t_npair[t] + 775LL * l.t_nlm[t] + 77LL * l.t_nsent[t] + 1807LL * l.t_nkf[t];
+        perm[t] = t;
+    }
+    // (LBA_DISPATCH_INDEX_ORDER: index order, for the tests that check the order changes no result)
+    if (!std::getenv("LBA_DISPATCH_INDEX_ORDER"))
+        std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return cost[x] > cost[y]; });
+    desc.assign(std::max(n_tiles, 1), TileDesc{});
+    std::atomic<int> bad_tile{-1}, bad_bf{-1};
+    par_for(SETUP_PIECES, [&](int piece) {
+        const Range r = piece_range(n_tiles, piece, SETUP_PIECES);
+        for (int w = r.lo; w < r.hi; ++w) {
+            const int t = perm[w];
+            TileDesc& d = desc[w];
+            d.tile = t;
+            d.obs0 = l.t_obs0[t]; d.nobs = l.t_nobs[t];
+            d.ts0 = l.t_smp0[t]; d.nts = l.t_nsmp[t];
+            d.pair0 = l.t_pair0[t]; d.npair = l.t_npair[t];
+            d.lm0 = l.t_lm0[t]; d.nlm = l.t_nlm[t];
+            d.sent0 = l.t_sent0[t]; d.nsent = l.t_nsent[t];
+            d.kf0 = l.t_kf0[t]; d.nkf = l.t_nkf[t];
+            d.q0 = pair_r0[d.pair0]; d.nq = pair_r0[d.pair0 + d.npair] - d.q0;
+            d.m0 = lm_r0[d.lm0]; d.nm = lm_r0[d.lm0 + d.nlm] - d.m0;
+            d.flags = t < n_stiles ? TD_STAGED : 0;
+            if (d.nts > TILE_SMP || d.nobs > TILE_OBS || d.nlm > TILE_LMS) {   // (tile_fits: never)
+                bad_tile = t;
+                continue;
+            }
+            for (int i = 0; i < d.nts; ++i) d.smp[i] = l.tsm_smp[d.ts0 + i];
+            // bf keyframe per tile sample (ob_row >> 16: the observation's tile sample, regular tiles only).  All
+            // observations of a pose sample read the bf of one keyframe: a GP sample belongs to one pair, so to
+            // one KF a, and a KF pose sample is n_gps + KF b.  Checked, since the kernel relies on it.
+            if (d.flags & TD_STAGED) {
+                for (int i = 0; i < d.nts; ++i) d.bfkf[i] = -1;
+                for (int q = d.obs0; q < d.obs0 + d.nobs; ++q) {
+                    const int kf = (ob_meta[q] & 15) <= LBA_STEREO_GP ? ob_kfa[q] : ob_kfb[q];
+                    int& slot = d.bfkf[ob_row[q] >> 16];
+                    if (slot >= 0 && slot != kf) bad_bf = t;
+                    slot = kf;
+                }
+                for (int i = 0; i < d.nts; ++i)
+                    if (d.bfkf[i] < 0) bad_bf = t;   // (a tile sample without an observation)
+            }
+        }
+    });
+    if (bad_tile >= 0)
+        throw ApiError{LBA_E_LIMIT, "internal: tile " + std::to_string(bad_tile.load()) + " exceeds the tile limits"};
+    if (bad_bf >= 0)
+        throw ApiError{LBA_E_LIMIT, "internal: the observations of a pose sample of tile " + std::to_string(bad_bf.load()) +
+                                        " disagree on their bf keyframe"};
+    rec.assign(std::max(n_obs, 1), ObsRec{});
+    par_for(SETUP_PIECES, [&](int piece) {
+        const Range rg = piece_range(n_obs, piece, SETUP_PIECES);
+        for (int q = rg.lo; q < rg.hi; ++q) {
+            ObsRec& r = rec[q];
+            r.meta = ob_meta[q]; r.row = ob_row[q]; r.smp = ob_smp[q]; r.lm = ob_lm[q];
+            r.kfa = ob_kfa[q]; r.kfb = ob_kfb[q];
+            for (int i = 0; i < 3; ++i) r.z[i] = ob_z[3 * (size_t)q + i];
+            r.w = ob_w[q];
+        }
+    });
 }
-std::vector<double>& scr_dbl(lba_problem* p, int k, size_t n) {
-    p->scr_d[k].resize(n);
-    return p->scr_d[k];
-}
 
-int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xyz, int n_lm, const lba_obs* obs,
-                int n_obs, const lba_prior* priors, int n_priors, const int32_t* vel_kfs, int n_vel,
-                const lba_cam* cams, int n_cam) {
-    if (n_kf < 0 || n_lm < 0 || n_obs < 0 || n_priors < 0 || n_vel < 0 || n_cam < 0)
-        throw ApiError{LBA_E_ARG, "negative array size"};
-    if ((n_kf && !kfs) || (n_lm && !lm_xyz) || (n_obs && !obs) || (n_priors && !priors) || (n_vel && !vel_kfs) ||
-        (n_cam && !cams))
-        throw ApiError{LBA_E_ARG, "null array with non-zero size"};
-    // the first invalid observation (pieces in parallel; the serial pass below names it).  The same pass counts each
-    // piece's observations per landmark (the counting sort into observations by landmark, below) and marks the
-    // keyframes the piece touches (activity): the caller's 64-byte records are read once for the three
-    constexpr int VP = SETUP_PIECES;
-    int first_bad = n_obs;
-    const bool lm_hist = n_lm > 0 && (long long)n_lm * VP <= (8LL << 20);   // (else: the serial counting sort)
-    std::vector<int>& lm_cnt = scr_int(p, 13, lm_hist ? (size_t)VP * n_lm : 0);
-    std::vector<char> kf_mark((size_t)VP * std::max(n_kf, 1), 0);
-    {
-        int bad_at[VP];
-        par_for(VP, [&](int piece) {
-            const int i0 = (int)((long long)n_obs * piece / VP), i1 = (int)((long long)n_obs * (piece + 1) / VP);
-            bad_at[piece] = n_obs;
-            int* hc = lm_hist ? lm_cnt.data() + (size_t)piece * n_lm : nullptr;
-            if (hc) std::fill(hc, hc + n_lm, 0);
-            char* km = kf_mark.data() + (size_t)piece * std::max(n_kf, 1);
-            for (int i = i0; i < i1; ++i) {
-                const lba_obs& o = obs[i];
-                bool ok = o.kind >= LBA_MONO_GP && o.kind <= LBA_STEREO && o.kf_b >= 0 && o.kf_b < n_kf && o.lm >= 0 &&
-                          o.lm < n_lm && o.cam >= 0 && o.cam < n_cam && o.cam <= 255;
-                if (ok && (o.kind == LBA_MONO_GP || o.kind == LBA_STEREO_GP))
-                    ok = o.kf_a >= 0 && o.kf_a < n_kf && o.kf_a != o.kf_b &&
-                         std::fabs(kfs[o.kf_b].time - kfs[o.kf_a].time) > 1e-6;
-                if (!ok) { bad_at[piece] = i; break; }
-                if (hc) ++hc[o.lm];
-                km[o.kf_b] = 1;
-                if (is_gp(o.kind)) km[o.kf_a] = 1;
-            }
-        });
-        for (int piece = 0; piece < VP; ++piece) first_bad = std::min(first_bad, bad_at[piece]);
-    }
-    for (int i = first_bad; i < n_obs; ++i) {
-        const lba_obs& o = obs[i];
-        if (o.kind < LBA_MONO_GP || o.kind > LBA_STEREO) throw ApiError{LBA_E_ARG, "obs " + std::to_string(i) + ": bad kind"};
-        if (o.kf_b < 0 || o.kf_b >= n_kf || o.lm < 0 || o.lm >= n_lm || o.cam < 0 || o.cam >= n_cam || o.cam > 255)
-            throw ApiError{LBA_E_ARG, "obs " + std::to_string(i) + ": index out of range"};
-        if (is_gp(o.kind)) {
-            if (o.kf_a < 0 || o.kf_a >= n_kf || o.kf_a == o.kf_b)
-                throw ApiError{LBA_E_ARG, "obs " + std::to_string(i) + ": bad kf_a"};
-            if (!(std::fabs(kfs[o.kf_b].time - kfs[o.kf_a].time) > 1e-6))   // QiInv assert (GaussianProcess.h:32)
-                throw ApiError{LBA_E_ARG, "obs " + std::to_string(i) + ": keyframe times too close"};
-        }
-    }
-    for (int i = 0; i < n_priors; ++i) {
-        const lba_prior& e = priors[i];
-        if (e.kf_a < 0 || e.kf_a >= n_kf || e.kf_b < 0 || e.kf_b >= n_kf || e.kf_a == e.kf_b)
-            throw ApiError{LBA_E_ARG, "prior " + std::to_string(i) + ": bad vertex"};
-        if (!(std::fabs(kfs[e.kf_b].time - kfs[e.kf_a].time) > 1e-6))
-            throw ApiError{LBA_E_ARG, "prior " + std::to_string(i) + ": keyframe times too close"};
-    }
-    for (int i = 0; i < n_vel; ++i)
-        if (vel_kfs[i] < 0 || vel_kfs[i] >= n_kf) throw ApiError{LBA_E_ARG, "velocity edge: bad vertex"};
-    std::vector<int> ext_cams;   // cameras with a free extrinsic, ascending (g2o vertex ids iniMPid + c + 1)
-    for (int c = 0; c < n_cam; ++c)
-        if (cams[c].ext_free) ext_cams.push_back(c);
-    if (!ext_cams.empty()) {
-        if (p->part_n > 0) throw ApiError{LBA_E_LIMIT, "free extrinsics are not supported in a partitioned problem"};
-        for (int i = 0; i < n_obs; ++i)   // EdgeStereoGP projects through the static MultiKeyFrame::mTbc
-            if (obs[i].kind == LBA_STEREO_GP && cams[obs[i].cam].ext_free)
-                throw ApiError{LBA_E_ARG, "obs " + std::to_string(i) + ": stereo GP observation of a camera with a free extrinsic"};
-    }
-
-    // LBA_SETUP_TIMING: wall time of the set-up phases on stderr (host preprocessing vs device upload)
-    const bool stime = std::getenv("LBA_SETUP_TIMING") != nullptr;
-    auto tlast = std::chrono::steady_clock::now();
-    p->setup_ms.clear();
-    auto tsub = tlast;
-    auto sub = [&](const char* what) {   // finer stamps inside a phase (LBA_SETUP_TIMING only)
-        if (!stime) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "    %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - tsub).count());
-        tsub = now;
-    };
-    auto mark = [&](const char* what) {
-        if (p->stream) flush_uploads(p);   // (the arrays staged in this phase go out while the next one runs)
-        const auto now = std::chrono::steady_clock::now();
-        const double ms = std::chrono::duration<double, std::milli>(now - tlast).count();
-        p->setup_ms.push_back(ms);
-        if (stime) std::fprintf(stderr, "set_problem %-12s %8.3f ms\n", what, ms);
-        tlast = tsub = now;
-    };
-    p->status_entered = false;
-    if (p->stream) HIPCHK(hipStreamSynchronize(p->stream));   // (the buffers are reused below)
-    free_all(p);
-    p->zero_list.clear();
-    p->n_kf = n_kf; p->n_lm = n_lm; p->n_obs = n_obs; p->n_cam = n_cam;
-    p->lm_host.assign(lm_xyz, lm_xyz + 3 * (size_t)n_lm);
-    p->kf_fixed.resize(n_kf);
-    for (int k = 0; k < n_kf; ++k) p->kf_fixed[k] = kfs[k].fixed != 0;
-
-    // ---- active vertices (SparseOptimizer::initializeOptimization: a vertex is active if an edge
-    //      that is not all-fixed touches it, sparse_optimizer.cpp:197-267)
-    std::vector<char> kf_act(n_kf, 0), lm_act(n_lm, 0);
-    for (int piece = 0; piece < VP; ++piece)
-        for (int k = 0; k < n_kf; ++k) kf_act[k] |= kf_mark[(size_t)piece * std::max(n_kf, 1) + k];
-    // observations by original landmark (stable): a counting sort, the counts from the validation pass
-    std::vector<int> lo0(n_lm + 1, 0);
-    std::vector<int>& lo_of = scr_int(p, 1, n_obs);
-    if (lm_hist) {
-        par_for(VP, [&](int piece) {   // per landmark: its total, and every piece's offset (its earlier pieces' counts)
-            for (int l = (int)((long long)n_lm * piece / VP); l < (int)((long long)n_lm * (piece + 1) / VP); ++l) {
-                int run = 0;
-                for (int q = 0; q < VP; ++q) {
-                    int& c = lm_cnt[(size_t)q * n_lm + l];
-                    const int v = c;
-                    c = run;
-                    run += v;
-                }
-                lo0[l + 1] = run;
-            }
-        });
-        for (int l = 0; l < n_lm; ++l) lo0[l + 1] += lo0[l];
-        par_for(VP, [&](int piece) {
-            int* off = lm_cnt.data() + (size_t)piece * n_lm;
-            for (int i = (int)((long long)n_obs * piece / VP); i < (int)((long long)n_obs * (piece + 1) / VP); ++i) {
-                const int l = obs[i].lm;
-                lo_of[lo0[l] + off[l]++] = i;
-            }
-        });
-    } else {
-        for (int i = 0; i < n_obs; ++i) lo0[obs[i].lm + 1]++;
-        for (int l = 0; l < n_lm; ++l) lo0[l + 1] += lo0[l];
-        std::vector<int> fill(lo0.begin(), lo0.end() - 1);
-        for (int i = 0; i < n_obs; ++i) lo_of[fill[obs[i].lm]++] = i;
-    }
-    for (int l = 0; l < n_lm; ++l) lm_act[l] = lo0[l + 1] > lo0[l];
-    std::vector<lba_prior> pri;
-    for (int i = 0; i < n_priors; ++i)
-        if (!(kfs[priors[i].kf_a].fixed && kfs[priors[i].kf_b].fixed)) {
-            pri.push_back(priors[i]);
-            kf_act[priors[i].kf_a] = kf_act[priors[i].kf_b] = 1;
-        }
-    std::vector<int> vel;
-    for (int i = 0; i < n_vel; ++i)
-        if (!kfs[vel_kfs[i]].fixed) {
-            vel.push_back(vel_kfs[i]);
-            kf_act[vel_kfs[i]] = 1;
-        }
-    // partitioned: every rank carries every non-fixed keyframe (activity is the union over the ranks'
-    // edges; the caller's global graph connects them all through the motion priors on rank 0)
-    if (p->part_n > 0)
-        for (int k = 0; k < n_kf; ++k)
-            if (!kfs[k].fixed) kf_act[k] = 1;
-    // free extrinsics (always active: their EdgeExtrinsicPrior is not all-fixed) as KF slots after the
-    // keyframes, pose blocks after the keyframes' (g2o orders the active vertices by id)
-    const int n_ext = (int)ext_cams.size(), n_kfs = n_kf + n_ext;
-    std::vector<int> cam_slot(n_cam, -1);
-    p->kf_hidx.assign(n_kfs, -1);
-    int n_pb = 0;
-    for (int k = 0; k < n_kf; ++k)
-        if (kf_act[k] && !kfs[k].fixed) p->kf_hidx[k] = n_pb++;
-    const int n_pb_kf = n_pb;
-    for (int e = 0; e < n_ext; ++e) {
-        cam_slot[ext_cams[e]] = n_kf + e;
-        p->kf_hidx[n_kf + e] = n_pb++;
-    }
-    p->n_ext = n_ext;
-    p->ext_cams = ext_cams;
-    p->cams.assign(cams, cams + n_cam);
-    p->n_pb = n_pb;
-    p->np = 12 * n_pb;
-    p->np_ext = 12 * n_pb_kf + 6 * n_ext;
-    p->pose_ext.assign(p->np, -1);
-    for (int i = 0; i < p->np; ++i)
-        if (i < 12 * n_pb_kf) p->pose_ext[i] = i;
-        else if (i % 12 < 6) p->pose_ext[i] = 12 * n_pb_kf + 6 * ((i - 12 * n_pb_kf) / 12) + i % 12;
-    // the extrinsic block an observation links (EdgeMonoGPExtrinsic's vertex 3), or -1
-    auto ext_block = [&](const lba_obs& o) { return o.kind == LBA_MONO_GP && cam_slot[o.cam] >= 0 ? p->kf_hidx[cam_slot[o.cam]] : -1; };
-    if ((p->cfg.flags & LBA_FLAG_DENSE_SOLVE) && p->np > CF_DENSE_MAX_NP * CHOL_NB)
-        throw ApiError{LBA_E_LIMIT, "the L^-1-tile solve is limited to pose systems of 6144"};
-    const std::vector<int>& H = p->kf_hidx;
-
-    sub("checks + activity");
-    // GP (prev KF, KF) pairs, numbered in order of first appearance; gp_of: each GP observation's pair
-    // (per KF b a short list of its pairs: (KF a, pair index); usually one, the previous keyframe)
-    // (in parallel: every piece lists its distinct pairs in first-appearance order; the pieces' lists, merged in
-    // piece order, give the pairs in first appearance over all observations; then every GP observation's pair)
-    std::vector<std::vector<std::pair<int, int>>> gp_by_b(n_kf);
-    std::vector<int> gp_a, gp_b, gp_of(n_obs, -1);
-    {
-        std::vector<std::vector<std::pair<int, int>>> first(VP);   // per piece: (kf_a, kf_b) in first-appearance order
-        par_for(VP, [&](int piece) {
-            std::vector<std::vector<int>> seen_a(n_kf);   // per KF b: the KFs a this piece has listed
-            auto& out = first[piece];
-            for (int i = (int)((long long)n_obs * piece / VP); i < (int)((long long)n_obs * (piece + 1) / VP); ++i) {
-                const lba_obs& o = obs[i];
-                if (!is_gp(o.kind)) continue;
-                std::vector<int>& sa = seen_a[o.kf_b];
-                if (std::find(sa.begin(), sa.end(), o.kf_a) != sa.end()) continue;
-                sa.push_back(o.kf_a);
-                out.emplace_back(o.kf_a, o.kf_b);
-            }
-        });
-        for (int piece = 0; piece < VP; ++piece)
-            for (const auto& ab : first[piece]) {
-                auto& lst = gp_by_b[ab.second];
-                bool have = false;
-                for (const auto& e : lst)
-                    if (e.first == ab.first) { have = true; break; }
-                if (have) continue;
-                lst.emplace_back(ab.first, (int)gp_a.size());
-                gp_a.push_back(ab.first);
-                gp_b.push_back(ab.second);
-            }
-        par_for(VP, [&](int piece) {
-            for (int i = (int)((long long)n_obs * piece / VP); i < (int)((long long)n_obs * (piece + 1) / VP); ++i) {
-                const lba_obs& o = obs[i];
-                if (!is_gp(o.kind)) continue;
-                for (const auto& e : gp_by_b[o.kf_b])
-                    if (e.first == o.kf_a) { gp_of[i] = e.second; break; }
-            }
-        });
-    }
-    sub("  GP pair numbering");
-
-    // GP pose samples: distinct observation times per GP pair (one per camera time stamp in
-    // LocalGPBA), contiguous per pair; observations of a camera with a free extrinsic get samples of
-    // their own (key: time, camera), so a sample couples at most one extrinsic block
-    std::vector<int> gp_s0(gp_a.size() + 1, 0), sample_of(n_obs, -1), gps_cam;
-    std::vector<double> gps_t;
-    {
-        typedef std::pair<double, int> SKey;
-        auto skey = [&](const lba_obs& o) { return SKey(o.t, ext_block(o) >= 0 ? o.cam : -1); };
-        // distinct keys per pair are few: each of 8 observation pieces keeps up to KC distinct keys per pair
-        // inline (flat arrays), more in a per-piece overflow list; then per pair the union, sorted
-        const int ng = (int)gp_a.size();
-        constexpr int KC = 16, NPC = SETUP_PIECES;
-        std::vector<SKey> pk((size_t)NPC * std::max(ng, 1) * KC);
-        std::vector<int> pc((size_t)NPC * std::max(ng, 1), 0);
-        std::vector<std::vector<std::pair<int, SKey>>> pov(NPC);
-        par_for(NPC, [&](int piece) {
-            SKey* K = pk.data() + (size_t)piece * ng * KC;
-            int* C = pc.data() + (size_t)piece * ng;
-            for (int i = (int)((long long)n_obs * piece / NPC); i < (int)((long long)n_obs * (piece + 1) / NPC); ++i)
-                if (is_gp(obs[i].kind)) {
-                    const int g = gp_of[i];
-                    const SKey k = skey(obs[i]);
-                    SKey* v = K + (size_t)g * KC;
-                    bool seen = false;
-                    for (int c = 0; c < C[g]; ++c)
-                        if (v[c] == k) { seen = true; break; }
-                    if (seen) continue;
-                    if (C[g] < KC) v[C[g]++] = k;
-                    else pov[piece].emplace_back(g, k);
-                }
-        });
-        std::vector<std::vector<SKey>> ts(ng);
-        for (int piece = 0; piece < NPC; ++piece) {
-            const SKey* K = pk.data() + (size_t)piece * ng * KC;
-            const int* C = pc.data() + (size_t)piece * ng;
-            for (int g = 0; g < ng; ++g) ts[g].insert(ts[g].end(), K + (size_t)g * KC, K + (size_t)g * KC + C[g]);
-            for (const auto& e : pov[piece]) ts[e.first].push_back(e.second);
-        }
-        sub("  GP sample keys");
-        std::vector<SKey> keys;
-        for (size_t g = 0; g < ts.size(); ++g) {
-            std::sort(ts[g].begin(), ts[g].end());
-            ts[g].erase(std::unique(ts[g].begin(), ts[g].end()), ts[g].end());
-            gp_s0[g + 1] = gp_s0[g] + (int)ts[g].size();
-            for (const SKey& k : ts[g]) { gps_t.push_back(k.first); gps_cam.push_back(k.second); keys.push_back(k); }
-        }
-        sub("  GP sample sort");
-        par_for(SETUP_PIECES, [&](int piece) {
-            for (int i = (int)((long long)n_obs * piece / SETUP_PIECES); i < (int)((long long)n_obs * (piece + 1) / SETUP_PIECES); ++i)
-                if (is_gp(obs[i].kind)) {
-                    const int g = gp_of[i];
-                    const SKey* b = keys.data() + gp_s0[g];
-                    sample_of[i] = gp_s0[g] + (int)(std::lower_bound(b, b + (gp_s0[g + 1] - gp_s0[g]), skey(obs[i])) - b);
-                }
-        });
-    }
-
-    sub("GP pairs + samples");
-    // pose sample of every observation: its GP sample, or the KF pose record n_gps + kf_b
-    const int n_gps = (int)gps_t.size(), n_smp = n_gps + n_kfs;
-    std::vector<int>& smp_of = scr_int(p, 0, n_obs);
-    par_for(VP, [&](int piece) {
-        for (int i = (int)((long long)n_obs * piece / VP); i < (int)((long long)n_obs * (piece + 1) / VP); ++i)
-            smp_of[i] = is_gp(obs[i].kind) ? sample_of[i] : n_gps + obs[i].kf_b;
-    });
-
-    // ---- heavy landmarks: a landmark whose observations / keyframes exceed one tile of k_lin_schur (a
-    //      long track: LocalGPBA adds every observation of a local point, up to every keyframe of the
-    //      window plus GP observations from non-keyframes, src/Optimizer.cc:1050-1200) is linearised in
-    //      segment tiles and merged / eliminated by k_expand (heavy_item); heavy landmarks go last in
-    //      device order.  tile_fits: the LDS limits of one k_lin_schur workgroup
-    auto tile_fits = [&](int no, int nr, int npair, int nlmt, int nkf, int ns, int ne) {
-        return no <= TILE_OBS && nr <= TILE_ROWS && npair <= TILE_PAIRS && nlmt <= TILE_LMS && nkf <= TILE_KF &&
-               ns <= TILE_SMP && ne <= TILE_PROWS;
-    };
-    // per landmark: the span of non-fixed KFs observing it (device order key), heavy or not
-    std::vector<int> lmin(n_lm, INT_MAX), lmax(n_lm, INT_MAX), lm_npl(n_lm, 0);
-    std::vector<char> heavy(n_lm, 0);
-    par_for(SETUP_PIECES, [&](int piece) {
-        // distinct pose blocks / samples of a landmark counted by stamping (stamp = landmark + 1)
-        std::vector<int> kst_((size_t)std::max(n_pb, 1), 0), sst_((size_t)std::max(n_gps + n_kfs, 1), 0);
-        // (plain pointers and per-landmark locals: through the vectors every int store could alias every int
-        // load, and the compiler reloaded the tables per observation)
-        int* __restrict__ kst = kst_.data();
-        int* __restrict__ sst = sst_.data();
-        const int* __restrict__ Hh = H.data();
-        const int* __restrict__ lo = lo_of.data();
-        const int* __restrict__ lz = lo0.data();
-        const int* __restrict__ so = smp_of.data();
-        const int* __restrict__ cslot = cam_slot.data();
-        for (int l = (int)((long long)n_lm * piece / SETUP_PIECES); l < (int)((long long)n_lm * (piece + 1) / SETUP_PIECES); ++l) {
-            if (!lm_act[l]) continue;
-            int nr = 0, ne = 0, npl = 0, ns = 0, mn = INT_MAX, mx = INT_MAX;
-            const int stamp = l + 1;
-            for (int q = lz[l]; q < lz[l + 1]; ++q) {
-                const int oi = lo[q];
-                const lba_obs& o = obs[oi];
-                const int hb = Hh[o.kf_b], ha = is_gp(o.kind) ? Hh[o.kf_a] : -1;
-                const int hx = (o.kind == LBA_MONO_GP && cslot[o.cam] >= 0) ? Hh[cslot[o.cam]] : -1;   // ext_block(o)
-                for (int k : {hb, ha})
-                    if (k >= 0) {
-                        mn = mn == INT_MAX ? k : std::min(mn, k);
-                        mx = mx == INT_MAX ? k : std::max(mx, k);
-                    }
-                for (int k : {hb, ha, hx})
-                    if (k >= 0 && kst[k] != stamp) { kst[k] = stamp; ++npl; }
-                ne += (hb >= 0) + (ha >= 0) + (hx >= 0);
-                nr += obs_dim(o.kind);
-                const int sm = so[oi];
-                if (sst[sm] != stamp) { sst[sm] = stamp; ++ns; }
-            }
-            lmin[l] = mn;
-            lmax[l] = mx;
-            heavy[l] = !tile_fits(lz[l + 1] - lz[l], nr, npl, 1, npl, ns, ne);
-            lm_npl[l] = npl;   // (its distinct pose blocks: its (KF, landmark) pairs below)
-        }
-    });
-    sub("heavy classification");
-    std::vector<int> order;
-    int n_heavy_lm = 0;
-    {   // stable order by (heavy, lmin, lmax) (INT_MAX = observed by fixed KFs only, after every block):
-        // three stable counting passes (lmax, lmin, heavy) over the active landmarks in index order
-        auto key = [&](int v) { return v == INT_MAX ? n_pb : v; };
-        std::vector<int> a, b;
-        a.reserve(n_lm);
-        for (int l = 0; l < n_lm; ++l)
-            if (lm_act[l]) { a.push_back(l); n_heavy_lm += heavy[l]; }
-        b.resize(a.size());
-        std::vector<int> cnt((size_t)std::max(n_pb + 2, 3));
-        auto pass = [&](auto kf, int nk) {
-            std::fill(cnt.begin(), cnt.begin() + nk + 1, 0);
-            for (int l : a) cnt[kf(l) + 1]++;
-            for (int k = 0; k < nk; ++k) cnt[k + 1] += cnt[k];
-            for (int l : a) b[cnt[kf(l)]++] = l;
-            a.swap(b);
-        };
-        pass([&](int l) { return key(lmax[l]); }, n_pb + 1);
-        pass([&](int l) { return key(lmin[l]); }, n_pb + 1);
-        pass([&](int l) { return (int)heavy[l]; }, 2);
-        order.swap(a);
-    }
-    const int nl = (int)order.size(), n_reg = nl - n_heavy_lm;
-    p->n_lm_dev = nl;
-    p->lm_orig = order;
-    p->lm_dev.assign(n_lm, -1);
-    for (int d = 0; d < nl; ++d) p->lm_dev[order[d]] = d;
-
-    sub("landmark order");
-    // observations grouped by device landmark (stable)
-    std::vector<int> lobs0(nl + 1, 0);
-    std::vector<int>& obs_of = scr_int(p, 2, n_obs);
-    for (int d = 0; d < nl; ++d) lobs0[d + 1] = lobs0[d] + (lo0[order[d] + 1] - lo0[order[d]]);
-    par_for(SETUP_PIECES, [&](int piece) {
-        for (int d = (int)((long long)nl * piece / SETUP_PIECES); d < (int)((long long)nl * (piece + 1) / SETUP_PIECES); ++d) {
-            const int l = order[d];
-            std::copy(lo_of.begin() + lo0[l], lo_of.begin() + lo0[l + 1], obs_of.begin() + lobs0[d]);
-        }
-    });
-
-    sub("obs by landmark");
-    // (KF, landmark) pairs, per device landmark, ascending pose block
-    std::vector<int> lm_pair0(nl + 1, 0), pair_lm, pair_kf;
-    auto lm_blocks = [&](int d, std::vector<int>& ks) {   // the landmark's pose blocks, ascending, distinct
-        ks.clear();
-        for (int q = lobs0[d]; q < lobs0[d + 1]; ++q) {
-            const lba_obs& o = obs[obs_of[q]];
-            if (H[o.kf_b] >= 0) ks.push_back(H[o.kf_b]);
-            if (is_gp(o.kind) && H[o.kf_a] >= 0) ks.push_back(H[o.kf_a]);
-            if (ext_block(o) >= 0) ks.push_back(ext_block(o));
-        }
-        std::sort(ks.begin(), ks.end());
-        ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
-    };
-    // counts (the distinct pose blocks the heavy classification counted), then the pairs themselves
-    for (int d = 0; d < nl; ++d) lm_pair0[d + 1] = lm_pair0[d] + lm_npl[order[d]];
-    const int n_pairs = lm_pair0[nl];
-    pair_lm.resize(n_pairs);
-    pair_kf.resize(n_pairs);
-    par_for(SETUP_PIECES, [&](int piece) {
-        std::vector<int> ks;
-        for (int d = (int)((long long)nl * piece / SETUP_PIECES); d < (int)((long long)nl * (piece + 1) / SETUP_PIECES); ++d) {
-            lm_blocks(d, ks);
-            for (size_t i = 0; i < ks.size(); ++i) { pair_lm[lm_pair0[d] + i] = d; pair_kf[lm_pair0[d] + i] = ks[i]; }
-        }
-    });
-    // lm_kfs[d]: the landmark's pose blocks (ascending) = its pairs' blocks
-    struct Span {
-        const int* p; size_t n;
-        const int* begin() const { return p; }
-        const int* end() const { return p + n; }
-        size_t size() const { return n; }
-        int operator[](size_t i) const { return p[i]; }
-    };
-    auto lm_kfs_at = [&](int d) { return Span{pair_kf.data() + lm_pair0[d], (size_t)(lm_pair0[d + 1] - lm_pair0[d])}; };
-    struct LmKfs {
-        decltype(lm_kfs_at)& f;
-        Span operator[](int d) const { return f(d); }
-    } lm_kfs{lm_kfs_at};
-
-    mark("order/pairs");
-    // ---- tiles: consecutive regular landmarks under the limits of one k_lin_schur workgroup (tile_fits),
-    //      then the segment tiles of the heavy landmarks
-    std::vector<int> t_obs0, t_nobs, t_lm0, t_nlm, t_pair0, t_npair, t_smp0, t_nsmp, t_sent0, t_nsent, t_kf0, t_nkf;
-    std::vector<int> tkf_list, tsm_smp, tsm_rows, sent_l1, sent_l2, sent_k1, sent_k2;
-    std::vector<int> ob_row(n_obs, 0);
-    std::vector<int> pair_r0(n_pairs + 1, 0), pair_rows, lm_r0(nl + 1, 0), lm_rows;
-    std::vector<int> pair_lk(std::max(n_pairs, 1), 0);   // regular pairs: tile-local KF | tile-local landmark << 8
-    // heavy landmarks: segments (landmark slots nl + s), segment pairs (pair slots n_pairs + c) and, per
-    // canonical pair of a heavy landmark, the segment pairs that sum into it
-    std::vector<int> hv_lm, hv_seg0(1, 0), hv_hp0(1, 0), hp_src0(1, 0), hp_src;
-    int n_stiles = 0, n_seg = 0, n_segpairs = 0;
-    {
-        // per observation in device order, what the tiling reads (contiguous instead of through obs_of):
-        // pose blocks of KF b / KF a / the extrinsic (-1: none or fixed), rows, pose sample
-        std::vector<int>&dhb = scr_int(p, 3, n_obs), &dha = scr_int(p, 4, n_obs), &dhx = scr_int(p, 5, n_obs),
-                         &ddim = scr_int(p, 6, n_obs), &dsmp = scr_int(p, 7, n_obs);
-        par_for(SETUP_PIECES, [&](int piece) {
-            for (int q = (int)((long long)n_obs * piece / SETUP_PIECES); q < (int)((long long)n_obs * (piece + 1) / SETUP_PIECES); ++q) {
-                const lba_obs& ob = obs[obs_of[q]];
-                dhb[q] = H[ob.kf_b];
-                dha[q] = is_gp(ob.kind) ? H[ob.kf_a] : -1;
-                dhx[q] = ext_block(ob);
-                ddim[q] = obs_dim(ob.kind);
-                dsmp[q] = smp_of[obs_of[q]];
-            }
-        });
-        sub("tile inputs");
-        std::vector<unsigned long long> tob;
-        // LDS rows of a tile's observations [q0, q1) grouped by pose sample: every sample of the tile owns
-        // one contiguous row run (stable by observation within a sample)
-        auto emit_rows = [&](int q0, int q1) {
-            tob.clear();
-            for (int q = q0; q < q1; ++q) tob.push_back(((unsigned long long)(unsigned)dsmp[q] << 32) | (unsigned)q);
-            std::sort(tob.begin(), tob.end());
-            t_smp0.push_back((int)tsm_smp.size());
-            int row = 0;
-            for (size_t i = 0; i < tob.size();) {
-                const int sm = (int)(tob[i] >> 32), r0 = row;
-                size_t j = i;
-                for (; j < tob.size() && (int)(tob[j] >> 32) == sm; ++j) {
-                    const int q = (int)(tob[j] & 0xffffffffu);
-                    ob_row[q] = row;
-                    row += ddim[q];
-                }
-                tsm_smp.push_back(sm);
-                tsm_rows.push_back(r0 | ((row - r0) << 16));
-                i = j;
-            }
-            t_nsmp.push_back((int)tsm_smp.size() - t_smp0.back());
-        };
-        // entry list of the pair of KF block k over observations [q0, q1) (tile-local observation | side << 16)
-        auto emit_pair_rows = [&](int k, int q0, int q1, int obase) {
-            for (int o = q0; o < q1; ++o) {
-                if (dhb[o] == k) pair_rows.push_back((o - obase) | (1 << 16));
-                if (dha[o] == k) pair_rows.push_back(o - obase);
-                if (dhx[o] == k) pair_rows.push_back((o - obase) | (2 << 16));
-            }
-        };
-        // regular tiles: the landmarks [0, n_reg) in SETUP_PIECES contiguous pieces, each cut greedily into tiles
-        // on its own thread (tiles never straddle a piece boundary, so the tiling is the same for any thread
-        // count).  The tiles' lists depend only on their own landmarks: they are built in a second pass, in
-        // parallel over runs of consecutive tiles, and concatenated with their offsets.  (A window below 256
-        // landmarks per piece is one piece: its cut is serial, its lists -- most of the work -- are not.)
-        struct TileOut {
-            std::vector<int> t_obs0, t_nobs, t_lm0, t_nlm, t_pair0, t_npair, t_smp0, t_nsmp, t_sent0, t_nsent, t_kf0,
-                t_nkf, tkf_list, tsm_smp, tsm_rows, sent_l1, sent_l2, sent_k1, sent_k2, pair_rows, lm_rows;
-        };
-        const int n_pieces = n_reg >= 256 * SETUP_PIECES ? SETUP_PIECES : 1;
-#ifndef LBA_TILE_OBS_CAP
-#define LBA_TILE_OBS_CAP TILE_OBS
-#endif
-        const int obs_cap = LBA_TILE_OBS_CAP;   // (a smaller cap: A/B builds only, scripts/exp_build.sh)
-        // pass 1, the cut: the first landmark of every tile, per piece
-        std::vector<std::vector<int>> cut(n_pieces);
-        par_for(n_pieces, [&](int piece) {
-            const int cap = obs_cap;
-            const int d_end = (int)((long long)n_reg * (piece + 1) / n_pieces);
-            int d = (int)((long long)n_reg * piece / n_pieces);
-            // the tile's sample / KF sets grow by the landmark's new elements, found through membership
-            // marks (1: in the tile, 2: new for the landmark being tried)
-            std::vector<int> uni, usm, new_s, new_k;
-            std::vector<char> kmark((size_t)std::max(n_pb, 1), 0), smark((size_t)std::max(n_smp, 1), 0);
-            uni.reserve(TILE_PAIRS + 8);
-            usm.reserve(TILE_SMP + 8);
-            while (d < d_end) {
-                int nobs = 0, rows = 0, npair = 0, nlmt = 0, nent = 0;
-                uni.clear();
-                usm.clear();
-                int e = d;
-                while (e < d_end) {
-                    int no = lobs0[e + 1] - lobs0[e], nr = 0, ne = 0;
-                    new_s.clear();
-                    new_k.clear();
-                    for (int q = lobs0[e]; q < lobs0[e + 1]; ++q) {
-                        nr += ddim[q];
-                        if (!smark[dsmp[q]]) { smark[dsmp[q]] = 2; new_s.push_back(dsmp[q]); }
-                        ne += (dhb[q] >= 0) + (dha[q] >= 0) + (dhx[q] >= 0);
-                    }
-                    for (int k : lm_kfs[e])
-                        if (!kmark[k]) { kmark[k] = 2; new_k.push_back(k); }
-                    const int npl = lm_pair0[e + 1] - lm_pair0[e];
-                    const bool fits = tile_fits(nobs + no, rows + nr, npair + npl, nlmt + 1,
-                                                (int)(uni.size() + new_k.size()), (int)(usm.size() + new_s.size()),
-                                                nent + ne) &&
-                                      (nlmt == 0 || nobs + no <= cap);
-                    for (int v : new_s) smark[v] = fits ? 1 : 0;
-                    for (int k : new_k) kmark[k] = fits ? 1 : 0;
-                    if (!fits) {
-                        if (e == d)   // (the heavy classification above takes every landmark a tile cannot hold)
-                            throw ApiError{LBA_E_LIMIT, "internal: landmark " + std::to_string(order[e]) + " does not fit a tile"};
-                        break;
-                    }
-                    nobs += no; rows += nr; npair += npl; nlmt += 1; nent += ne;
-                    usm.insert(usm.end(), new_s.begin(), new_s.end());
-                    uni.insert(uni.end(), new_k.begin(), new_k.end());
-                    ++e;
-                }
-                for (int v : usm) smark[v] = 0;
-                for (int k : uni) kmark[k] = 0;
-                cut[piece].push_back(d);
-                d = e;
-            }
-        });
-        std::vector<int> tl_d;   // tile t: landmarks [tl_d[t], tl_d[t + 1])
-        for (const auto& c : cut) tl_d.insert(tl_d.end(), c.begin(), c.end());
-        const int n_rt = (int)tl_d.size();
-        tl_d.push_back(n_reg);
-        // pass 2, the lists: n_runs runs of consecutive tiles
-        const int n_runs = std::min(SETUP_PIECES, n_rt);
-        auto run_t0 = [&](int r) { return (int)((long long)n_rt * r / n_runs); };
-        std::vector<TileOut> outs(n_runs);
-        par_for(n_runs, [&](int run) {
-            TileOut& T = outs[run];
-            const int ta = run_t0(run), tb = run_t0(run + 1);
-            std::vector<int> uni, usm;
-            std::vector<char> kmark((size_t)std::max(n_pb, 1), 0), smark((size_t)std::max(n_smp, 1), 0);
-            std::vector<int> sloc_v((size_t)std::max(n_smp, 1), 0);   // sample -> its rank in the tile
-            int* sloc = sloc_v.data();
-            int srows[TILE_SMP + 1];
-            uni.reserve(TILE_PAIRS + 8);
-            usm.reserve(TILE_SMP + 8);
-            {   // capacity for the run's share of the outputs (no regrowth while building)
-                const int la = tl_d[ta], lb = tl_d[tb];
-                const int no_p = lobs0[lb] - lobs0[la], np_p = lm_pair0[lb] - lm_pair0[la];
-                const int nt_est = tb - ta + 1;
-                T.pair_rows.reserve((size_t)np_p * 4 + 16);
-                T.lm_rows.reserve((size_t)no_p * 3 + 16);
-                T.tsm_smp.reserve((size_t)nt_est * TILE_SMP / 2);
-                T.tsm_rows.reserve((size_t)nt_est * TILE_SMP / 2);
-                T.sent_l1.reserve((size_t)nt_est * 48); T.sent_l2.reserve((size_t)nt_est * 48);
-                T.sent_k1.reserve((size_t)nt_est * 48); T.sent_k2.reserve((size_t)nt_est * 48);
-                T.tkf_list.reserve((size_t)nt_est * TILE_KF);
-            }
-            for (int t = ta; t < tb; ++t) {
-                const int d = tl_d[t], e = tl_d[t + 1];
-                const int nobs = lobs0[e] - lobs0[d], npair = lm_pair0[e] - lm_pair0[d], nlmt = e - d;
-                // the tile's pose blocks (uni) and pose samples (usm), sorted
-                uni.clear();
-                usm.clear();
-                for (int l = d; l < e; ++l) {
-                    for (int q = lobs0[l]; q < lobs0[l + 1]; ++q)
-                        if (!smark[dsmp[q]]) { smark[dsmp[q]] = 1; usm.push_back(dsmp[q]); }
-                    for (int k : lm_kfs[l])
-                        if (!kmark[k]) { kmark[k] = 1; uni.push_back(k); }
-                }
-                for (int v : usm) smark[v] = 0;
-                for (int k : uni) kmark[k] = 0;
-                std::sort(uni.begin(), uni.end());
-                std::sort(usm.begin(), usm.end());
-                for (size_t i = 0; i < usm.size(); ++i) sloc[usm[i]] = (int)i;
-                T.t_obs0.push_back(lobs0[d]); T.t_nobs.push_back(nobs);
-                T.t_lm0.push_back(d); T.t_nlm.push_back(nlmt);
-                T.t_pair0.push_back(lm_pair0[d]); T.t_npair.push_back(npair);
-                T.t_kf0.push_back((int)T.tkf_list.size()); T.t_nkf.push_back((int)uni.size());
-                for (int k : uni) T.tkf_list.push_back(k);
-                auto local = [&](int k) { return (int)(std::lower_bound(uni.begin(), uni.end(), k) - uni.begin()); };
-                // LDS rows grouped by pose sample: every sample of the tile owns one contiguous row run, the
-                // samples ascending, observations ascending within a sample (a counting pass over the
-                // tile's sorted sample list)
-                T.t_smp0.push_back((int)T.tsm_smp.size());
-                {
-                    const int ns = (int)usm.size();
-                    std::fill(srows, srows + ns + 1, 0);
-                    for (int q = lobs0[d]; q < lobs0[e]; ++q) srows[sloc[dsmp[q]] + 1] += ddim[q];
-                    for (int i = 0; i < ns; ++i) srows[i + 1] += srows[i];
-                    for (int i = 0; i < ns; ++i) {
-                        T.tsm_smp.push_back(usm[i]);
-                        T.tsm_rows.push_back(srows[i] | ((srows[i + 1] - srows[i]) << 16));
-                    }
-                    for (int q = lobs0[d]; q < lobs0[e]; ++q) {
-                        const int i = sloc[dsmp[q]];
-                        ob_row[q] = srows[i] | (i << 16);   // (+ the tile-local sample: k_update's back-substitution)
-                        srows[i] += ddim[q];
-                    }
-                }
-                T.t_nsmp.push_back((int)T.tsm_smp.size() - T.t_smp0.back());
-                // entry lists per pair, row lists per landmark, the pairs' tile-local (KF, landmark);
-                // pair_r0 / lm_r0 hold run-local offsets until the concatenation below
-                for (int l = d; l < e; ++l) {
-                    for (int q = lm_pair0[l]; q < lm_pair0[l + 1]; ++q) {
-                        const int k = pair_kf[q];
-                        for (int o = lobs0[l]; o < lobs0[l + 1]; ++o) {
-                            if (dhb[o] == k) T.pair_rows.push_back((o - lobs0[d]) | (1 << 16));
-                            if (dha[o] == k) T.pair_rows.push_back(o - lobs0[d]);
-                            if (dhx[o] == k) T.pair_rows.push_back((o - lobs0[d]) | (2 << 16));
-                        }
-                        pair_r0[q + 1] = (int)T.pair_rows.size();
-                        pair_lk[q] = local(k) | ((l - d) << 8);
-                    }
-                    for (int o = lobs0[l]; o < lobs0[l + 1]; ++o)
-                        for (int r = 0; r < ddim[o]; ++r) T.lm_rows.push_back((ob_row[o] & 0xffff) + r);
-                    lm_r0[l + 1] = (int)T.lm_rows.size();
-                }
-                // Schur entries: every (k1 <= k2) pose-block pair co-observed by a landmark of the tile, in
-                // (k1, k2) order (k_lin_schur writes C's blocks of exactly these KF pairs)
-                {
-                    bool co[TILE_KF][TILE_KF] = {};
-                    int lk[TILE_KF];
-                    for (int l = d; l < e; ++l) {
-                        const Span ks = lm_kfs[l];
-                        for (size_t a = 0; a < ks.size(); ++a) lk[a] = local(ks[a]);
-                        for (size_t a = 0; a < ks.size(); ++a)
-                            for (size_t b = a; b < ks.size(); ++b) co[lk[a]][lk[b]] = true;
-                    }
-                    const int nu = (int)uni.size();
-                    T.t_sent0.push_back((int)T.sent_l1.size());
-                    int nen = 0;
-                    // the diagonal entries (every tile KF has one) first: k_lin_schur gives them 6 tasks (their
-                    // strictly lower 6 x 6 corner is never assembled), the others 8
-                    for (int i = 0; i < nu; ++i) {
-                        ++nen;
-                        T.sent_l1.push_back(i); T.sent_l2.push_back(i);
-                        T.sent_k1.push_back(uni[i]); T.sent_k2.push_back(uni[i]);
-                    }
-                    for (int i = 0; i < nu; ++i)
-                        for (int j = i + 1; j < nu; ++j)
-                            if (co[i][j]) {
-                                ++nen;
-                                T.sent_l1.push_back(i); T.sent_l2.push_back(j);
-                                T.sent_k1.push_back(uni[i]); T.sent_k2.push_back(uni[j]);
-                            }
-                    T.t_nsent.push_back(nen);
-                }
-            }
-        });
-        // the runs' lists concatenated: every output's per-run offsets first, then the runs copied in parallel
-        // (a serial element-wise concatenation cost most of the tiling's wall time on 16 threads)
-        {
-            std::vector<TileOut*> po(n_runs);
-            for (int run = 0; run < n_runs; ++run) po[run] = &outs[run];
-            struct Cat {
-                std::vector<int>* dst;
-                std::vector<int> TileOut::*src;
-                int add;   // 0: values as they are; 1 / 2 / 3: + the run's offset into tsm_smp / sent_l1 / tkf_list
-            };
-            const Cat cats[] = {
-                {&t_obs0, &TileOut::t_obs0, 0}, {&t_nobs, &TileOut::t_nobs, 0}, {&t_lm0, &TileOut::t_lm0, 0},
-                {&t_nlm, &TileOut::t_nlm, 0}, {&t_pair0, &TileOut::t_pair0, 0}, {&t_npair, &TileOut::t_npair, 0},
-                {&t_smp0, &TileOut::t_smp0, 1}, {&t_nsmp, &TileOut::t_nsmp, 0}, {&t_sent0, &TileOut::t_sent0, 2},
-                {&t_nsent, &TileOut::t_nsent, 0}, {&t_kf0, &TileOut::t_kf0, 3}, {&t_nkf, &TileOut::t_nkf, 0},
-                {&tkf_list, &TileOut::tkf_list, 0}, {&tsm_smp, &TileOut::tsm_smp, 0}, {&tsm_rows, &TileOut::tsm_rows, 0},
-                {&sent_l1, &TileOut::sent_l1, 0}, {&sent_l2, &TileOut::sent_l2, 0}, {&sent_k1, &TileOut::sent_k1, 0},
-                {&sent_k2, &TileOut::sent_k2, 0}, {&pair_rows, &TileOut::pair_rows, 0}, {&lm_rows, &TileOut::lm_rows, 0}};
-            constexpr int NC = (int)(sizeof(cats) / sizeof(cats[0]));
-            // off[c][run]: where the run's part of output c starts
-            std::vector<std::vector<size_t>> off(NC, std::vector<size_t>(n_runs + 1, 0));
-            for (int c = 0; c < NC; ++c) {
-                for (int run = 0; run < n_runs; ++run)
-                    off[c][run + 1] = off[c][run] + (po[run]->*(cats[c].src)).size();
-                cats[c].dst->resize(off[c][n_runs]);
-            }
-            auto at = [&](std::vector<int> TileOut::*m) {   // index of an output in cats
-                for (int c = 0; c < NC; ++c)
-                    if (cats[c].src == m) return c;
-                return -1;
-            };
-            const int c_smp = at(&TileOut::tsm_smp), c_sent = at(&TileOut::sent_l1), c_kf = at(&TileOut::tkf_list);
-            const int c_pr = at(&TileOut::pair_rows), c_lr = at(&TileOut::lm_rows);
-            par_for(n_runs, [&](int run) {
-                const TileOut& T = *po[run];
-                for (int c = 0; c < NC; ++c) {
-                    const std::vector<int>& src = T.*(cats[c].src);
-                    const int a = cats[c].add == 1 ? (int)off[c_smp][run] : cats[c].add == 2 ? (int)off[c_sent][run]
-                                : cats[c].add == 3 ? (int)off[c_kf][run] : 0;
-                    int* d = cats[c].dst->data() + off[c][run];
-                    for (size_t k = 0; k < src.size(); ++k) d[k] = src[k] + a;
-                }
-                const int d0 = tl_d[run_t0(run)], d1 = tl_d[run_t0(run + 1)];
-                const int o_pr = (int)off[c_pr][run], o_lr = (int)off[c_lr][run];
-                for (int q = lm_pair0[d0]; q < lm_pair0[d1]; ++q) pair_r0[q + 1] += o_pr;
-                for (int l = d0; l < d1; ++l) lm_r0[l + 1] += o_lr;
-            });
-        }
-        n_stiles = (int)t_obs0.size();
-        sub("regular tiles");
-        // heavy landmarks: their canonical pairs and landmark slots get no rows of their own
-        for (int q = lm_pair0[n_reg]; q < n_pairs; ++q) pair_r0[q + 1] = (int)pair_rows.size();
-        for (int l = n_reg; l < nl; ++l) lm_r0[l + 1] = (int)lm_rows.size();
-        // segments: runs of a heavy landmark's observations under the limits of k_lin_schur's phases 1-4
-        // (no elimination: no KF-union limit; a segment's pairs are its distinct pose blocks)
-        std::vector<int> uni, usm;
-        std::vector<char> kmark((size_t)std::max(n_pb, 1), 0), smark((size_t)std::max(n_smp, 1), 0);
-        for (int l = n_reg; l < nl; ++l) {
-            hv_lm.push_back(l);
-            const int cp0 = lm_pair0[l], ncp = lm_pair0[l + 1] - cp0;
-            std::vector<std::vector<int>> src(ncp);
-            int q0 = lobs0[l];
-            while (q0 < lobs0[l + 1]) {
-                int q1 = q0, nr = 0, ne = 0;
-                usm.clear();
-                uni.clear();
-                while (q1 < lobs0[l + 1]) {
-                    const int neq = (dhb[q1] >= 0) + (dha[q1] >= 0) + (dhx[q1] >= 0);
-                    const int ns = (int)usm.size() + !smark[dsmp[q1]];
-                    int nk = (int)uni.size();
-                    for (int k : {dhb[q1], dha[q1], dhx[q1]})
-                        if (k >= 0 && !kmark[k]) { kmark[k] = 2; ++nk; }
-                    const bool fits = q1 - q0 + 1 <= TILE_OBS && nr + ddim[q1] <= TILE_ROWS && nk <= TILE_PAIRS &&
-                                      ns <= TILE_SMP && ne + neq <= TILE_PROWS;
-                    for (int k : {dhb[q1], dha[q1], dhx[q1]})
-                        if (k >= 0 && kmark[k] == 2) {
-                            kmark[k] = fits ? 1 : 0;
-                            if (fits) uni.push_back(k);
-                        }
-                    if (!fits) break;
-                    if (!smark[dsmp[q1]]) { smark[dsmp[q1]] = 1; usm.push_back(dsmp[q1]); }
-                    nr += ddim[q1];
-                    ne += neq;
-                    ++q1;
-                }
-                for (int v : usm) smark[v] = 0;
-                for (int k : uni) kmark[k] = 0;
-                std::sort(uni.begin(), uni.end());
-                const int s = n_seg++, sp0 = n_segpairs;
-                t_obs0.push_back(q0); t_nobs.push_back(q1 - q0);
-                t_lm0.push_back(nl + s); t_nlm.push_back(1);
-                t_pair0.push_back(n_pairs + sp0); t_npair.push_back((int)uni.size());
-                t_kf0.push_back((int)tkf_list.size()); t_nkf.push_back(0);
-                t_sent0.push_back((int)sent_l1.size()); t_nsent.push_back(0);
-                emit_rows(q0, q1);
-                for (size_t c = 0; c < uni.size(); ++c) {
-                    emit_pair_rows(uni[c], q0, q1, q0);
-                    pair_r0.push_back((int)pair_rows.size());
-                    const int* kb = pair_kf.data() + cp0;
-                    src[std::lower_bound(kb, kb + ncp, uni[c]) - kb].push_back(n_pairs + sp0 + (int)c);
-                }
-                n_segpairs += (int)uni.size();
-                for (int o = q0; o < q1; ++o)
-                    for (int r = 0; r < ddim[o]; ++r) lm_rows.push_back(ob_row[o] + r);
-                lm_r0.push_back((int)lm_rows.size());
-                q0 = q1;
-            }
-            hv_seg0.push_back(n_seg);
-            for (int j = 0; j < ncp; ++j) {
-                for (int v : src[j]) hp_src.push_back(v);
-                hp_src0.push_back((int)hp_src.size());
-            }
-            hv_hp0.push_back(hv_hp0.back() + ncp);
-        }
-    }
-    const int n_tiles = (int)t_obs0.size();
-    const int n_sent = (int)sent_l1.size();
-    const int n_heavy = (int)hv_lm.size();
-
-    mark("tiles");
-    // ---- partial-sum slots, sorted by reduction target
-    // (tile, sample) M / g partials: per sample, its tiles in tile order
-    std::vector<int> mcnt(n_smp + 1, 0);
-    for (int sm : tsm_smp) mcnt[sm]++;
-    auto prefix = [](const std::vector<int>& c) {
-        std::vector<int> s(c.size(), 0);
-        for (size_t i = 1; i < c.size(); ++i) s[i] = s[i - 1] + c[i - 1];
-        return s;
-    };
-    std::vector<int> ms0 = prefix(mcnt), mfill(ms0);
-    std::vector<int> tsm_meta(2 * std::max(tsm_smp.size(), (size_t)1), 0);
-    for (size_t i = 0; i < tsm_smp.size(); ++i) {
-        tsm_meta[2 * i] = tsm_rows[i];
-        tsm_meta[2 * i + 1] = mfill[tsm_smp[i]]++;
-    }
-    const int n_mslots = ms0[n_smp];
-    // Hpp / b_p slab entries: pose samples (N^T M N: aa, ab, bb over their KFs a, b), then motion priors,
-    // then velocity edges
-    const int n_ublocks = n_pb * (n_pb + 1) / 2;
-    std::vector<int> ub_i(n_ublocks), ub_j(n_ublocks);
-    for (int bi = 0; bi < n_pb; ++bi)
-        for (int bj = bi; bj < n_pb; ++bj) {
-            const int id = ublock_id(n_pb, bi, bj);
-            ub_i[id] = bi; ub_j[id] = bj;
-        }
-    // (a sample of a camera with a free extrinsic also couples its block e: ae, be, ee, b_e; then the
-    // extrinsic priors on their blocks as "b")
-    std::vector<int> ent_a, ent_b, ent_e, ent_cam;
-    for (int sm = 0; sm < n_smp; ++sm) {
-        ent_e.push_back(-1); ent_cam.push_back(-1);
-        if (mcnt[sm] == 0) { ent_a.push_back(-1); ent_b.push_back(-1); continue; }   // unobserved
-        if (sm < n_gps) {
-            const int g = (int)(std::upper_bound(gp_s0.begin(), gp_s0.end(), sm) - gp_s0.begin()) - 1;
-            ent_a.push_back(H[gp_a[g]]); ent_b.push_back(H[gp_b[g]]);
-            if (gps_cam[sm] >= 0) { ent_e.back() = H[cam_slot[gps_cam[sm]]]; ent_cam.back() = gps_cam[sm]; }
-        } else {
-            ent_a.push_back(-1); ent_b.push_back(H[sm - n_gps]);
-        }
-    }
-    for (auto& e : pri) { ent_a.push_back(H[e.kf_a]); ent_b.push_back(H[e.kf_b]); ent_e.push_back(-1); ent_cam.push_back(-1); }
-    for (int k : vel) { ent_a.push_back(-1); ent_b.push_back(H[k]); ent_e.push_back(-1); ent_cam.push_back(-1); }
-    for (int e = 0; e < n_ext; ++e) { ent_a.push_back(-1); ent_b.push_back(H[n_kf + e]); ent_e.push_back(-1); ent_cam.push_back(-1); }
-    const int n_entries = (int)ent_a.size();
-    std::vector<int> hcnt(n_ublocks + 1, 0), gcnt(n_pb + 1, 0);
-    for (int en = 0; en < n_entries; ++en) {
-        const int a = ent_a[en], b = ent_b[en], x = ent_e[en];
-        if (a >= 0) { hcnt[ublock_id(n_pb, a, a)]++; gcnt[a]++; }
-        if (b >= 0) { hcnt[ublock_id(n_pb, b, b)]++; gcnt[b]++; }
-        if (a >= 0 && b >= 0) hcnt[ublock_id(n_pb, std::min(a, b), std::max(a, b))]++;
-        if (x >= 0) {   // extrinsic blocks follow every KF block: (a, x), (b, x) are upper as they stand
-            hcnt[ublock_id(n_pb, x, x)]++; gcnt[x]++;
-            if (a >= 0) hcnt[ublock_id(n_pb, a, x)]++;
-            if (b >= 0) hcnt[ublock_id(n_pb, b, x)]++;
-        }
-    }
-    std::vector<int> hs0 = prefix(hcnt), gs0 = prefix(gcnt);
-    std::vector<int> hfill(hs0), gfill(gs0);
-    std::vector<int> seg_slot(SEG_STRIDE * (size_t)std::max(n_entries, 1), -1),
-        seg_gslot(GSEG_STRIDE * (size_t)std::max(n_entries, 1), -1);
-    for (int en = 0; en < n_entries; ++en) {
-        const int a = ent_a[en], b = ent_b[en], x = ent_e[en];
-        int* sl = seg_slot.data() + SEG_STRIDE * (size_t)en;
-        int* gl = seg_gslot.data() + GSEG_STRIDE * (size_t)en;
-        sl[3] = 0;
-        if (a >= 0) { sl[0] = hfill[ublock_id(n_pb, a, a)]++; gl[0] = gfill[a]++; }
-        if (a >= 0 && b >= 0) { sl[1] = hfill[ublock_id(n_pb, std::min(a, b), std::max(a, b))]++; sl[3] = a > b; }
-        if (b >= 0) { sl[2] = hfill[ublock_id(n_pb, b, b)]++; gl[1] = gfill[b]++; }
-        if (x >= 0) {
-            if (a >= 0) sl[4] = hfill[ublock_id(n_pb, a, x)]++;
-            if (b >= 0) sl[5] = hfill[ublock_id(n_pb, b, x)]++;
-            sl[6] = hfill[ublock_id(n_pb, x, x)]++;
-            sl[7] = ent_cam[en];
-            gl[2] = gfill[x]++;
-        }
-    }
-    // the pose sample that writes each Hpp / b_p slot (fused expansion + assembly; -1: an edge item)
-    std::vector<int> hs_prod(std::max(hs0[n_ublocks], 1), -1), gs_prod(std::max(gs0[n_pb], 1), -1);
-    for (int en = 0; en < n_smp; ++en) {
-        const int* sl = seg_slot.data() + SEG_STRIDE * (size_t)en;
-        const int* gl = seg_gslot.data() + GSEG_STRIDE * (size_t)en;
-        for (int q : {0, 1, 2, 4, 5, 6})
-            if (sl[q] >= 0) hs_prod[sl[q]] = en;
-        for (int q = 0; q < 3; ++q)
-            if (gl[q] >= 0) gs_prod[gl[q]] = en;
-    }
-    // Schur partial blocks per (tile, KF pair) and rhs partials per (tile, KF)
-    std::vector<int> scnt(n_ublocks + 1, 0), gpcnt(n_pb + 1, 0);
-    for (int s = 0; s < n_sent; ++s) scnt[ublock_id(n_pb, sent_k1[s], sent_k2[s])]++;
-    for (int k : tkf_list) gpcnt[k]++;
-    for (int h = 0; h < n_heavy; ++h) {   // a heavy landmark: every pair (a <= b) of its KFs, every KF
-        const Span ks = lm_kfs[hv_lm[h]];
-        for (size_t a = 0; a < ks.size(); ++a) {
-            gpcnt[ks[a]]++;
-            for (size_t b = a; b < ks.size(); ++b) scnt[ublock_id(n_pb, ks[a], ks[b])]++;
-        }
-    }
-    std::vector<int> ss0 = prefix(scnt), gps0 = prefix(gpcnt);
-    std::vector<int> sfill(ss0), gpfill(gps0);
-    std::vector<int> sslot(std::max(n_sent, 1)), tkf_gslot(std::max((int)tkf_list.size(), 1));
-    for (int s = 0; s < n_sent; ++s) sslot[s] = sfill[ublock_id(n_pb, sent_k1[s], sent_k2[s])]++;
-    for (size_t t = 0; t < tkf_list.size(); ++t) tkf_gslot[t] = gpfill[tkf_list[t]]++;
-    std::vector<int> hv_ss0(1, 0), hv_sslot, hp_gslot;   // (after the regular tiles' slots of each target)
-    for (int h = 0; h < n_heavy; ++h) {
-        const Span ks = lm_kfs[hv_lm[h]];
-        for (size_t a = 0; a < ks.size(); ++a) {
-            hp_gslot.push_back(gpfill[ks[a]]++);
-            for (size_t b = a; b < ks.size(); ++b) hv_sslot.push_back(sfill[ublock_id(n_pb, ks[a], ks[b])]++);
-        }
-        hv_ss0.push_back((int)hv_sslot.size());
-    }
-    const int n_hslots = hs0[n_ublocks], n_gslots = gs0[n_pb], n_sslots = ss0[n_ublocks], n_gpslots = gps0[n_pb];
-    sub("slab slots");
-
-
-    // ---- observations in device order
-    std::vector<int>&ob_meta = scr_int(p, 8, n_obs), &ob_kfa = scr_int(p, 9, n_obs), &ob_kfb = scr_int(p, 10, n_obs),
-                     &ob_smp = scr_int(p, 11, n_obs), &ob_lm = scr_int(p, 12, n_obs);
-    std::vector<double>&ob_z = scr_dbl(p, 0, 3 * (size_t)n_obs), &ob_w = scr_dbl(p, 1, n_obs);
-    p->obs_dev.assign(n_obs, -1);
-    par_for(SETUP_PIECES, [&](int piece) {
-    for (int q = (int)((long long)n_obs * piece / SETUP_PIECES); q < (int)((long long)n_obs * (piece + 1) / SETUP_PIECES); ++q) {
-        const lba_obs& o = obs[obs_of[q]];
-        p->obs_dev[obs_of[q]] = q;
-        ob_meta[q] = o.kind | (o.cam << 4);
-        ob_kfa[q] = is_gp(o.kind) ? o.kf_a : -1;
-        ob_kfb[q] = o.kf_b;
-        ob_smp[q] = smp_of[obs_of[q]];
-        ob_lm[q] = p->lm_dev[o.lm];
-        ob_z[3 * (size_t)q] = o.z[0]; ob_z[3 * (size_t)q + 1] = o.z[1]; ob_z[3 * (size_t)q + 2] = o.z[2];
-        ob_w[q] = o.w;
-    }
-    });
-    sub("device-order observations");
-    // cameras: Tcb = Tbc^-1 as matrix (MultiKeyFrame::mTbc[c].cast<double>() normalises) and the
-    // extrinsic factor Ad(Tbc) (lba::cam_record)
-    std::vector<double> camd(CAMD_STRIDE * (size_t)std::max(n_cam, 1), 0.0);
-    auto cam_se3 = [&](int c) {
-        SE3 T;
-        double q[4];
-        normalize_q(cams[c].q, q);
-        T.q = Quat{q[0], q[1], q[2], q[3]};
-        for (int i = 0; i < 3; ++i) T.t[i] = cams[c].t[i];
-        return T;
-    };
-    for (int c = 0; c < n_cam; ++c)
-        cam_record(cam_se3(c), cams[c].fx, cams[c].fy, cams[c].cx, cams[c].cy, camd.data() + CAMD_STRIDE * c);
-    // keyframe / landmark state (then the free extrinsics: Tbc as the pose, no velocity)
-    std::vector<double> kst(KF_STRIDE * (size_t)std::max(n_kfs, 1), 0.0), lst(3 * (size_t)std::max(nl, 1), 0.0);
-    for (int k = 0; k < n_kf; ++k) {
-        double* o = kst.data() + KF_STRIDE * k;
-        normalize_q(kfs[k].q, o);
-        for (int i = 0; i < 3; ++i) o[4 + i] = kfs[k].t[i];
-        for (int i = 0; i < 6; ++i) o[7 + i] = kfs[k].vel[i];
-        o[13] = kfs[k].time;
-        o[14] = kfs[k].bf;
-    }
-    std::vector<int> kf_cam(std::max(n_kfs, 1), -1), ep_kf(std::max(n_ext, 1), 0);
-    std::vector<double> ep_data(16 * (size_t)std::max(n_ext, 1), 0.0);
-    for (int e = 0; e < n_ext; ++e) {
-        const int c = ext_cams[e];
-        const SE3 T = cam_se3(c);
-        double* o = kst.data() + KF_STRIDE * (size_t)(n_kf + e);
-        o[0] = T.q.x; o[1] = T.q.y; o[2] = T.q.z; o[3] = T.q.w;
-        for (int i = 0; i < 3; ++i) o[4 + i] = T.t[i];
-        kf_cam[n_kf + e] = c;
-        ep_kf[e] = n_kf + e;
-        // EdgeExtrinsicPrior(R): R_ = R.inverse() of the widened, normalised mRbc_ini (so3.hpp:229-231)
-        double qi[4];
-        normalize_q(cams[c].rbc_ini, qi);
-        const Quat ri = qinv(Quat{qi[0], qi[1], qi[2], qi[3]});
-        double* d = ep_data.data() + 16 * (size_t)e;
-        d[0] = ri.x; d[1] = ri.y; d[2] = ri.z; d[3] = ri.w;
-        for (int i = 0; i < 9; ++i) d[4 + i] = cams[c].rbc_info[i];
-    }
-    for (int d = 0; d < nl; ++d)
-        for (int i = 0; i < 3; ++i) lst[3 * (size_t)d + i] = lm_xyz[3 * (size_t)order[d] + i];
-    std::vector<int> pri_a, pri_b;
-    for (auto& e : pri) { pri_a.push_back(e.kf_a); pri_b.push_back(e.kf_b); }
-
-    mark("slots/state");
-    if (p->host_only) {   // (lba_setup_host_profile) a fingerprint of the tiling and the slab layout
-        uint32_t h = 2166136261u;
-        auto mix = [&](const std::vector<int>& v) {
-            for (int x : v) { h ^= (uint32_t)x; h *= 16777619u; }
-        };
-        mix(t_obs0); mix(t_lm0); mix(tsm_meta); mix(pair_rows); mix(lm_rows); mix(pair_lk); mix(sent_l1); mix(sent_l2);
-        mix(sslot); mix(tkf_gslot); mix(seg_slot); mix(ob_row);
-        mix(t_nobs); mix(t_nlm); mix(t_pair0); mix(t_npair); mix(t_smp0); mix(t_nsmp); mix(t_sent0); mix(t_nsent);
-        mix(t_kf0); mix(t_nkf); mix(tkf_list); mix(sent_k1); mix(sent_k2); mix(pair_r0); mix(lm_r0);
-        p->setup_hash = h;
-        p->setup_tiles = n_tiles;
-        // the largest tile shapes (lba_setup_tile_shapes): regular tiles in [0..8], segment tiles in [9..13]
-        int32_t* sh = p->setup_shapes;
-        std::fill(sh, sh + LBA_TILE_SHAPES, 0);
-        auto up = [](int32_t& m, int v) { m = std::max<int32_t>(m, v); };
-        for (int t = 0; t < n_tiles; ++t) {
-            const bool reg = t < n_stiles;
-            const int rows = lm_r0[t_lm0[t] + t_nlm[t]] - lm_r0[t_lm0[t]];
-            int srows = 0;
-            for (int s = t_smp0[t]; s < t_smp0[t] + t_nsmp[t]; ++s) srows = std::max(srows, tsm_rows[s] >> 16);
-            ++sh[reg ? 0 : 9];
-            up(sh[reg ? 1 : 10], t_nobs[t]);
-            up(sh[reg ? 2 : 11], rows);
-            up(sh[reg ? 3 : 12], t_nsmp[t]);
-            if (reg) {
-                up(sh[4], srows);
-                up(sh[5], t_nlm[t]);
-                up(sh[6], t_npair[t]);
-                up(sh[7], t_nkf[t]);
-                up(sh[8], t_nsent[t]);
-            } else {
-                up(sh[13], t_npair[t]);
-            }
-        }
-        return LBA_OK;
-    }
-    // ---- device upload
+// ---- device half 1: the window's read-only arrays and the partial-sum slabs
+void upload_window(lba_problem* p, const Window& W, const Vertices& V, const GpSamples& G, const LmOrder& L,
+                   const Tiles& T, const Slots& S, const DevOrder& O) {
+    const SetupScratch& scr = p->scr;
+    const TileLists& l = T.l;
+    const std::vector<int>&gp_a = G.gp_a, &gp_b = G.gp_b;
+    const int n_obs = W.n_obs, n_kfs = V.n_kfs, n_tiles = T.n_tiles(), n_gps = G.n_gps, n_smp = G.n_smp;
     DevProblem& D = p->D;
-    D.n_kf = n_kfs; D.n_kf_user = n_kf; D.n_eprior = n_ext; D.n_lm = nl; D.n_obs = n_obs; D.n_gp = (int)gp_a.size(); D.n_pairs = n_pairs;
-    D.n_tiles = n_tiles; D.n_pb = n_pb; D.np = p->np; D.n_prior = (int)pri.size(); D.n_vel = (int)vel.size();
-    D.n_cam = n_cam; D.n_entries = n_entries; D.n_sentries = n_sent; D.n_ublocks = n_ublocks;
-    D.ob_meta = dupload(p, ob_meta); D.ob_kfa = dupload(p, ob_kfa); D.ob_kfb = dupload(p, ob_kfb);
-    D.ob_smp = dupload(p, ob_smp); D.ob_lm = dupload(p, ob_lm);
-    D.ob_row = dupload(p, ob_row);
-    D.ob_z = dupload(p, ob_z); D.ob_w = dupload(p, ob_w);
-    D.gp_s0 = dupload(p, gp_s0); D.gps_t = dupload(p, gps_t); D.n_gps = n_gps; D.n_smp = n_smp;
+    D.n_kf = n_kfs; D.n_kf_user = W.n_kf; D.n_eprior = V.n_ext; D.n_lm = L.nl; D.n_obs = n_obs; D.n_gp = (int)gp_a.size(); D.n_pairs = L.n_pairs;
+    D.n_tiles = n_tiles; D.n_pb = V.n_pb; D.np = p->np; D.n_prior = (int)V.pri.size(); D.n_vel = (int)V.vel.size();
+    D.n_cam = W.n_cam; D.n_entries = S.n_entries; D.n_sentries = (int)l.sent_l1.size(); D.n_ublocks = S.n_ublocks;
+    D.ob_meta = dupload(p, scr.ob_meta); D.ob_kfa = dupload(p, scr.ob_kfa); D.ob_kfb = dupload(p, scr.ob_kfb);
+    D.ob_smp = dupload(p, scr.ob_smp); D.ob_lm = dupload(p, scr.ob_lm);
+    D.ob_row = dupload(p, scr.ob_row);
+    D.ob_z = dupload(p, scr.ob_z); D.ob_w = dupload(p, scr.ob_w);
+    D.gp_s0 = dupload(p, G.gp_s0); D.gps_t = dupload(p, G.gps_t); D.n_gps = n_gps; D.n_smp = n_smp;
     D.kf_hidx = dupload(p, p->kf_hidx); D.gp_kfa = dupload(p, gp_a); D.gp_kfb = dupload(p, gp_b);
     {   // per GP pair: KF a, KF b and their pose blocks (k_update's trial states: one load, no kf_hidx hop)
         std::vector<int> hab(4 * std::max(gp_a.size(), (size_t)1), -1);
@@ -1594,111 +527,47 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
         }
         D.gp_hab = dupload(p, hab);
     }
-    D.camdb[0] = dupload(p, camd);
-    D.camdb[1] = dupload(p, camd);
-    D.kf_cam = dupload(p, kf_cam);
-    D.ep_kf = dupload(p, ep_kf);
-    D.ep_data = dupload(p, ep_data);
-    D.tile_obs0 = dupload(p, t_obs0); D.tile_nobs = dupload(p, t_nobs); D.tile_lm0 = dupload(p, t_lm0);
-    D.tile_nlm = dupload(p, t_nlm); D.tile_pair0 = dupload(p, t_pair0); D.tile_npair = dupload(p, t_npair);
-    D.tile_smp0 = dupload(p, t_smp0); D.tile_nsmp = dupload(p, t_nsmp); D.tsm_meta = dupload(p, tsm_meta);
-    D.ms0 = dupload(p, ms0); D.tile_sent0 = dupload(p, t_sent0);
-    D.tile_nsent = dupload(p, t_nsent); D.tile_kf0 = dupload(p, t_kf0); D.tile_nkf = dupload(p, t_nkf);
-    D.tkf_list = dupload(p, tkf_list);
-    {   // k_lin_schur's workgroup -> tile order (applied to its descriptors below): longest first by a cost estimate (list scheduling: the tiles
-        // outnumber the resident workgroup slots, ~1.4x at config 1, and the costly tiles, many KFs and Schur
-        // entries, sit at the end of the landmark order, so in index order the last round of workgroups ran
-        // long after most CUs were idle).  Cost: a non-negative least-squares fit of measured tile durations
-        // on the tile shape (us ~ 0.027 npair + 0.775 nlm + 0.077 nsent + 1.807 nkf, profiles/r3aq_tile_order.txt)
-        std::vector<long long> cost(n_tiles);
-        std::vector<int> perm(n_tiles);
-        for (int t = 0; t < n_tiles; ++t) {
-            cost[t] = 27LL * t_npair[t] + 775LL * t_nlm[t] + 77LL * t_nsent[t] + 1807LL * t_nkf[t];
-            perm[t] = t;
-        }
-        // (LBA_DISPATCH_INDEX_ORDER: index order, for the tests that check the order changes no result)
-        if (!std::getenv("LBA_DISPATCH_INDEX_ORDER"))
-            std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return cost[x] > cost[y]; });
-        // k_lin_schur's packed inputs (lba_device.hpp): the tile descriptors in this dispatch order and one record
-        // per observation
-        std::vector<TileDesc> desc(std::max(n_tiles, 1), TileDesc{});
-        std::atomic<int> bad_tile{-1}, bad_bf{-1};
-        par_for(SETUP_PIECES, [&](int piece) {
-            for (int w = (int)((long long)n_tiles * piece / SETUP_PIECES); w < (int)((long long)n_tiles * (piece + 1) / SETUP_PIECES); ++w) {
-                const int t = perm[w];
-                TileDesc& d = desc[w];
-                d.tile = t;
-                d.obs0 = t_obs0[t]; d.nobs = t_nobs[t];
-                d.ts0 = t_smp0[t]; d.nts = t_nsmp[t];
-                d.pair0 = t_pair0[t]; d.npair = t_npair[t];
-                d.lm0 = t_lm0[t]; d.nlm = t_nlm[t];
-                d.sent0 = t_sent0[t]; d.nsent = t_nsent[t];
-                d.kf0 = t_kf0[t]; d.nkf = t_nkf[t];
-                d.q0 = pair_r0[d.pair0]; d.nq = pair_r0[d.pair0 + d.npair] - d.q0;
-                d.m0 = lm_r0[d.lm0]; d.nm = lm_r0[d.lm0 + d.nlm] - d.m0;
-                d.flags = t < n_stiles ? TD_STAGED : 0;
-                if (d.nts > TILE_SMP || d.nobs > TILE_OBS || d.nlm > TILE_LMS) {   // (tile_fits: never)
-                    bad_tile = t;
-                    continue;
-                }
-                for (int i = 0; i < d.nts; ++i) d.smp[i] = tsm_smp[d.ts0 + i];
-                // bf keyframe per tile sample (ob_row >> 16: the observation's tile sample, regular tiles only).  All
-                // observations of a pose sample read the bf of one keyframe: a GP sample belongs to one pair, so to
-                // one KF a, and a KF pose sample is n_gps + KF b.  Checked, since the kernel relies on it.
-                if (d.flags & TD_STAGED) {
-                    for (int i = 0; i < d.nts; ++i) d.bfkf[i] = -1;
-                    for (int q = d.obs0; q < d.obs0 + d.nobs; ++q) {
-                        const int kf = (ob_meta[q] & 15) <= LBA_STEREO_GP ? ob_kfa[q] : ob_kfb[q];
-                        int& slot = d.bfkf[ob_row[q] >> 16];
-                        if (slot >= 0 && slot != kf) bad_bf = t;
-                        slot = kf;
-                    }
-                    for (int i = 0; i < d.nts; ++i)
-                        if (d.bfkf[i] < 0) bad_bf = t;   // (a tile sample without an observation)
-                }
-            }
-        });
-        if (bad_tile >= 0)
-            throw ApiError{LBA_E_LIMIT, "internal: tile " + std::to_string(bad_tile.load()) + " exceeds the tile limits"};
-        if (bad_bf >= 0)
-            throw ApiError{LBA_E_LIMIT, "internal: the observations of a pose sample of tile " + std::to_string(bad_bf.load()) +
-                                            " disagree on their bf keyframe"};
-        std::vector<ObsRec> rec(std::max(n_obs, 1), ObsRec{});
-        par_for(SETUP_PIECES, [&](int piece) {
-            for (int q = (int)((long long)n_obs * piece / SETUP_PIECES); q < (int)((long long)n_obs * (piece + 1) / SETUP_PIECES); ++q) {
-                ObsRec& r = rec[q];
-                r.meta = ob_meta[q]; r.row = ob_row[q]; r.smp = ob_smp[q]; r.lm = ob_lm[q];
-                r.kfa = ob_kfa[q]; r.kfb = ob_kfb[q];
-                for (int i = 0; i < 3; ++i) r.z[i] = ob_z[3 * (size_t)q + i];
-                r.w = ob_w[q];
-            }
-        });
+    D.camdb[0] = dupload(p, O.camd);
+    D.camdb[1] = dupload(p, O.camd);
+    D.kf_cam = dupload(p, O.kf_cam);
+    D.ep_kf = dupload(p, O.ep_kf);
+    D.ep_data = dupload(p, O.ep_data);
+    D.tile_obs0 = dupload(p, l.t_obs0); D.tile_nobs = dupload(p, l.t_nobs); D.tile_lm0 = dupload(p, l.t_lm0);
+    D.tile_nlm = dupload(p, l.t_nlm); D.tile_pair0 = dupload(p, l.t_pair0); D.tile_npair = dupload(p, l.t_npair);
+    D.tile_smp0 = dupload(p, l.t_smp0); D.tile_nsmp = dupload(p, l.t_nsmp); D.tsm_meta = dupload(p, S.tsm_meta);
+    D.ms0 = dupload(p, S.ms0); D.tile_sent0 = dupload(p, l.t_sent0);
+    D.tile_nsent = dupload(p, l.t_nsent); D.tile_kf0 = dupload(p, l.t_kf0); D.tile_nkf = dupload(p, l.t_nkf);
+    D.tkf_list = dupload(p, l.tkf_list);
+    {
+        std::vector<TileDesc> desc;
+        std::vector<ObsRec> rec;
+        pack_dispatch(T, scr, n_obs, desc, rec);
         D.tile_desc = dupload(p, desc);
         D.ob_rec = dupload(p, rec);
     }
-    D.n_stiles = n_stiles; D.n_heavy = n_heavy;
-    D.hv_lm = dupload(p, hv_lm); D.hv_seg0 = dupload(p, hv_seg0); D.hv_hp0 = dupload(p, hv_hp0);
-    D.hp_src0 = dupload(p, hp_src0); D.hp_src = dupload(p, hp_src); D.hp_gslot = dupload(p, hp_gslot);
-    D.hv_ss0 = dupload(p, hv_ss0); D.hv_sslot = dupload(p, hv_sslot);
-    D.Vh = dalloc<double>(p, (size_t)36 * std::max(hv_hp0.back(), 1));
-    D.pair_lk = dupload(p, pair_lk);
-    D.sent_l1 = dupload(p, sent_l1); D.sent_l2 = dupload(p, sent_l2);
-    D.pair_lm = dupload(p, pair_lm); D.pair_kf = dupload(p, pair_kf); D.pair_r0 = dupload(p, pair_r0);
-    D.pair_rows = dupload(p, pair_rows); D.lm_r0 = dupload(p, lm_r0); D.lm_rows = dupload(p, lm_rows);
-    D.lm_pair0 = dupload(p, lm_pair0);
+    D.n_stiles = T.n_stiles; D.n_heavy = (int)T.hv_lm.size();
+    D.hv_lm = dupload(p, T.hv_lm); D.hv_seg0 = dupload(p, T.hv_seg0); D.hv_hp0 = dupload(p, T.hv_hp0);
+    D.hp_src0 = dupload(p, T.hp_src0); D.hp_src = dupload(p, T.hp_src); D.hp_gslot = dupload(p, S.hp_gslot);
+    D.hv_ss0 = dupload(p, S.hv_ss0); D.hv_sslot = dupload(p, S.hv_sslot);
+    D.Vh = dalloc<double>(p, (size_t)36 * std::max(T.hv_hp0.back(), 1));
+    D.pair_lk = dupload(p, scr.pair_lk);
+    D.sent_l1 = dupload(p, l.sent_l1); D.sent_l2 = dupload(p, l.sent_l2);
+    D.pair_lm = dupload(p, L.pair_lm); D.pair_kf = dupload(p, L.pair_kf); D.pair_r0 = dupload(p, scr.pair_r0);
+    D.pair_rows = dupload(p, l.pair_rows); D.lm_r0 = dupload(p, scr.lm_r0); D.lm_rows = dupload(p, l.lm_rows);
+    D.lm_pair0 = dupload(p, L.lm_pair0);
     {   // k_update's sample-space back-substitution of the regular tiles' landmarks
         // per tile sample (tile order, beside tsm_smp): its sample's pose blocks and extrinsic camera
-        std::vector<int> tsm_blk(4 * std::max(tsm_smp.size(), (size_t)1), -1);
-        for (size_t j = 0; j < tsm_smp.size(); ++j) {
-            const int sm = tsm_smp[j];
-            tsm_blk[4 * j] = ent_a[sm];
-            tsm_blk[4 * j + 1] = ent_b[sm];
-            tsm_blk[4 * j + 2] = ent_e[sm];
-            tsm_blk[4 * j + 3] = ent_cam[sm];
+        std::vector<int> tsm_blk(4 * std::max(l.tsm_smp.size(), (size_t)1), -1);
+        for (size_t j = 0; j < l.tsm_smp.size(); ++j) {
+            const int sm = l.tsm_smp[j];
+            tsm_blk[4 * j] = S.ent_a[sm];
+            tsm_blk[4 * j + 1] = S.ent_b[sm];
+            tsm_blk[4 * j + 2] = S.ent_e[sm];
+            tsm_blk[4 * j + 3] = S.ent_cam[sm];
         }
-        D.tsm_smp = dupload(p, tsm_smp);
+        D.tsm_smp = dupload(p, l.tsm_smp);
         D.tsm_blk = dupload(p, tsm_blk);
-        D.lm_obs0 = dupload(p, lobs0);
+        D.lm_obs0 = dupload(p, L.lobs0);
     }
     D.hfin = p->d_hfin;
     D.hlog = p->d_hlog;
@@ -1715,12 +584,12 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
         HIPCHK(hipMemsetAsync(D.tdbg_chol, 0, (size_t)nblk * 16 * 8, p->stream));
         HIPCHK(hipMemsetAsync(D.tdbg_bs, 0, (size_t)nblk * 16 * 8, p->stream));
     }
-    D.seg_slot = dupload(p, seg_slot); D.seg_gslot = dupload(p, seg_gslot);
+    D.seg_slot = dupload(p, S.seg_slot); D.seg_gslot = dupload(p, S.seg_gslot);
 
-    D.hs0 = dupload(p, hs0); D.gs0 = dupload(p, gs0); D.ub_i = dupload(p, ub_i); D.ub_j = dupload(p, ub_j);
-    D.sslot = dupload(p, sslot); D.ss0 = dupload(p, ss0); D.tkf_gslot = dupload(p, tkf_gslot);
-    D.gps0 = dupload(p, gps0);
-    D.pri_a = dupload(p, pri_a); D.pri_b = dupload(p, pri_b); D.vel_kf = dupload(p, vel);
+    D.hs0 = dupload(p, S.hs0); D.gs0 = dupload(p, S.gs0); D.ub_i = dupload(p, S.ub_i); D.ub_j = dupload(p, S.ub_j);
+    D.sslot = dupload(p, S.sslot); D.ss0 = dupload(p, S.ss0); D.tkf_gslot = dupload(p, S.tkf_gslot);
+    D.gps0 = dupload(p, S.gps0);
+    D.pri_a = dupload(p, O.pri_a); D.pri_b = dupload(p, O.pri_b); D.vel_kf = dupload(p, V.vel);
     D.pri_entry0 = n_smp;
     double qcinv[36];
     if (!inverse6(p->cfg.qc, qcinv)) throw ApiError{LBA_E_ARG, "Qc is singular"};
@@ -1731,405 +600,231 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
     {   // pose samples; the KF records' factor N = [0 | I 0] is constant (k_gp_prep writes their poses)
         std::vector<double> g0((size_t)GPS_STRIDE * std::max(n_smp, 1), 0.0);
         for (int k = 0; k < n_kfs; ++k)
-            for (int l = 0; l < 6; ++l) g0[(size_t)(n_gps + k) * GPS_STRIDE + 12 + 6 * (12 + l) + l] = 1.0;
+            for (int l6 = 0; l6 < 6; ++l6) g0[(size_t)(n_gps + k) * GPS_STRIDE + 12 + 6 * (12 + l6) + l6] = 1.0;
         D.gpsb[0] = dupload(p, g0);
         D.gpsb[1] = dupload(p, g0);
     }
-    D.mslab = dalloc<double>(p, (size_t)MS_PITCH * std::max(n_mslots, 1));
+    D.mslab = dalloc<double>(p, (size_t)MS_PITCH * std::max(S.n_mslots, 1));
     D.kfp_pose = dalloc<double>(p, (size_t)KFP_STRIDE * std::max(n_kfs, 1));
-    D.hslab = dalloc<double>(p, (size_t)144 * std::max(n_hslots, 1));
-    D.gslab = dalloc<double>(p, (size_t)GS_PITCH * std::max(n_gslots, 1));
-    D.sslab = dalloc<double>(p, (size_t)144 * std::max(n_sslots, 1));
-    D.gpslab = dalloc<double>(p, (size_t)GS_PITCH * std::max(n_gpslots, 1));
-    D.n_mslots = n_mslots; D.n_hslots = n_hslots; D.n_gslots = n_gslots; D.n_sslots = n_sslots; D.n_gpslots = n_gpslots;
-    const int npad = (p->np + CHOL_NB - 1) / CHOL_NB * CHOL_NB;
-    mark("upload");
-    // ---- solve layout of the reduced camera system: dissection order, tile structure of L, task lists
-    {
-        const int NP = npad / CHOL_NB;
-        // natural tile pattern of S at panel granularity (structural blocks, diagonal), then the nested-
-        // dissection order and the symbolic factorisation (lba_plan.hpp).  Panels holding rows of free
-        // extrinsics (dense: they couple every keyframe) are ordered last.  A partition plans the union
-        // pattern of its ranks' systems.
-        const int NPk = std::min(NP, 12 * n_pb_kf / CHOL_NB + (n_ext ? 0 : NP));
-        std::vector<std::vector<int>> lower(NP);
-        for (int P = 0; P < NP; ++P) lower[P].push_back(P);
-        std::vector<std::pair<int, int>> edge_panels;   // (this rank's edges' couplings: the split's check)
-        auto couple = [&](int r, int c) {   // natural rows r, c of S
-            const int P = std::max(r, c) / CHOL_NB, Q = std::min(r, c) / CHOL_NB;
-            lower[P].push_back(Q);
-            edge_panels.emplace_back(P, Q);
-        };
-        for (int u = 0; u < n_ublocks; ++u) {
-            if (!(hcnt[u] > 0 || scnt[u] > 0)) continue;
-            const int r0 = 12 * ub_j[u], c0 = 12 * ub_i[u];
-            couple(r0, c0); couple(r0 + 11, c0); couple(r0, c0 + 11); couple(r0 + 11, c0 + 11);
-        }
-        for (int P = 0; P < NP; ++P) {
-            std::sort(lower[P].begin(), lower[P].end());
-            lower[P].erase(std::unique(lower[P].begin(), lower[P].end()), lower[P].end());
-        }
-        if (p->part_n > 0) part_status(p, 0);   // (every rank's preprocessing succeeded, or all throw)
-        if (p->part_n > 0) {   // the union pattern of the ranks' systems (one all-reduce, at set-up)
-            std::vector<double> occ((size_t)NP * NP, 0.0);
-            for (int P = 0; P < NP; ++P)
-                for (int Q : lower[P]) occ[(size_t)P * NP + Q] = 1.0;
-            double* d = dalloc<double>(p, occ.size());
-            HIPCHK(hipMemcpy(d, occ.data(), occ.size() * sizeof(double), hipMemcpyHostToDevice));
-            preduce(p, d, (int64_t)occ.size());
-            HIPCHK(hipStreamSynchronize(p->stream));
-            HIPCHK(hipMemcpy(occ.data(), d, occ.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (int P = 0; P < NP; ++P) {
-                lower[P].clear();
-                for (int Q = 0; Q <= P; ++Q)
-                    if (occ[(size_t)P * NP + Q] != 0.0 || Q == P) lower[P].push_back(Q);
-            }
-        }
-        sub("  S pattern");
-        const lba_plan::Plan& pl = plan_panels_cached(p->plan_cache, NP, NPk, lower);
-        sub("  dissection plan");
-        p->chain = pl.chain;
-        p->nd_tail = pl.tail;
-        p->nd_levels = pl.levels;
-        // distributed factorisation (LBA_FLAG_SUBTREE_SOLVE, partitioned problems): the elimination tree cut into
-        // one subtree per rank plus the top (lba_plan::split_subtrees, the same on every rank); this rank's
-        // couplings must lie in its subtree and the top (lba_partition_assign gives such a landmark split)
-        const bool split = p->part_n > 0 && (p->cfg.flags & LBA_FLAG_SUBTREE_SOLVE);
-        const std::vector<int> own = split ? lba_plan::split_subtrees(pl, p->part_n) : std::vector<int>(NP, -1);
-        if (split) {   // (a second status point: a rank whose couplings leave its subtree releases its peers)
-            bool stray = false;
-            for (const auto& e : edge_panels) {
-                const int a = own[pl.ppos[e.first]], b = own[pl.ppos[e.second]];
-                if ((a >= 0 && a != p->part_rank) || (b >= 0 && b != p->part_rank)) stray = true;
-            }
-            part_status(p, stray ? 1 : 0);
-            if (stray)
-                throw ApiError{LBA_E_ARG, "partitioned problem: a landmark or edge of rank " +
-                                              std::to_string(p->part_rank) + " couples keyframes of another rank's "
-                                              "subtree (split the window with lba_partition_assign)"};
-        }
-        p->split_own = own;
-        p->ppos_h = pl.ppos;
-        {   // the factorisation work this rank does: its subtree's columns and the top (split), or all of them
-            const double b3 = (double)CHOL_NB * CHOL_NB * CHOL_NB;
-            double f = 0.0;
-            int n_own = 0, n_top = 0;
-            for (int j = 0; j < NP; ++j) {
-                if (own[j] >= 0 && own[j] != p->part_rank) continue;
-                (own[j] < 0 ? n_top : n_own)++;
-                const double m = (double)pl.colrows[j].size();
-                f += b3 / 3.0 + m * b3 + m * b3 + m * (m - 1.0) * b3;
-            }
-            p->flops_factor_rank = f;
-            p->split_panels[0] = split ? n_own : 0;
-            p->split_panels[1] = split ? n_top : NP;
-        }
-        p->s_tiles = 0;
-        for (int P = 0; P < NP; ++P) p->s_tiles += (int)lower[P].size();
-        {   // per column with m tiles below the diagonal: potrf 32^3/3, m trsm 32^3, the m(m+1)/2 tile updates
-            // of the trailing matrix (syrk 32^3 on the diagonal ones, gemm 2 x 32^3 below)
-            const double b3 = (double)CHOL_NB * CHOL_NB * CHOL_NB;
-            double f = 0.0;
-            for (int j = 0; j < NP; ++j) {
-                const double m = (double)pl.colrows[j].size();
-                f += b3 / 3.0 + m * b3 + m * b3 + m * (m - 1.0) * b3;
-            }
-            p->flops_factor = f;
-        }
-        const std::vector<int>& ppos = pl.ppos;
-        const std::vector<int>& pnat = pl.pnat;
-        // rows: natural -> factorisation order, and back
-        std::vector<int> rpos(npad), rnat(npad);
-        for (int r = 0; r < npad; ++r) {
-            rpos[r] = ppos[r / CHOL_NB] * CHOL_NB + r % CHOL_NB;
-            rnat[rpos[r]] = r;
-        }
-        // solve path: L^-1 tiles (the solve has no substitution chain, but L^-1 is dense below the
-        // diagonal: O(n^3) work) up to CF_AUTO_BAND_NP panels, substitution tasks above (or when asked)
-        const bool band = split || (!(p->cfg.flags & LBA_FLAG_DENSE_SOLVE) &&
-                                    ((p->cfg.flags & LBA_FLAG_BAND_SOLVE) || NP > CF_AUTO_BAND_NP));
-        D.cf_band = band ? 1 : 0;
-        const int ntile = pl.ntile();
-        // dataflow factorisation + solve (k_chol_flow), tasks in topological order: per column c the
-        // factor tiles of its rows (the diagonal first), then (L^-1 solve) the L^-1 tiles of row c; at the
-        // end one solution task per panel.  Task t: (j, i, kind) with five tile ids (task_t) and a list of
-        // update / term entries (plist) with three tile ids each (plist_t).
-        // Distributed factorisation: list A (launch 0) holds this rank's subtree columns and its contributions to
-        // the top, list B (launch 1) the top columns (updated from top panels only: the subtrees' updates are summed
-        // into the top tiles between the launches) and the back substitution of the top and this rank's columns.
-#ifndef LBA_CF_LA_MAX_LIST   // (A/B builds only, scripts/exp_build.sh)
-#define LBA_CF_LA_MAX_LIST 16
-#endif
-        {
-            struct TaskList {
-                std::vector<int> tasks, task_i, task_t, pl0{0}, plist, plist_t;
-            } LA, LB;
-            TaskList* cur = &LA;
-            std::vector<int>&tasks = LA.tasks, &task_i = LA.task_i, &task_t = LA.task_t, &pl0 = LA.pl0, &plist = LA.plist,
-                            &plist_t = LA.plist_t;
-            auto add_task = [&](int j, int i, int kind, int la, int t0, int t1, int t2, int t3, int t4) {
-                cur->tasks.push_back(j | (kind << 24) | (la << 28));
-                cur->task_i.push_back(i);
-                cur->task_t.push_back(t0); cur->task_t.push_back(t1); cur->task_t.push_back(t2); cur->task_t.push_back(t3);
-                cur->task_t.push_back(t4);
-            };
-            auto add_entry = [&](int e, int t0, int t1, int t2) {
-                cur->plist.push_back(e);
-                cur->plist_t.push_back(t0); cur->plist_t.push_back(t1); cur->plist_t.push_back(t2);
-            };
-            auto end_task = [&]() { cur->pl0.push_back((int)cur->plist.size()); };
-            // (split) the panels whose updates a column of owner o takes inside its launch: its own subtree's, or the
-            // top's for a top column
-            auto same_part = [&](int pp, int o) { return !split || own[pp] == o; };
-            const std::vector<int>& rank = pl.rank;
-            auto by_rank = [&](int x, int y) { return rank[x] < rank[y]; };
-            // row c's columns below the diagonal
-            auto rowcols = [&](int c) {
-                return std::vector<int>(pl.cols.begin() + pl.rowptr[c], pl.cols.begin() + pl.rowptr[c + 1] - 1);
-            };
-            // structure of L^-1 (L^-1 solve only): Linv(i,j) != 0 iff some k in [j, i) with L(i,k) != 0 has
-            // Linv(k,j) != 0
-            std::vector<std::vector<char>> nzi(band ? 0 : NP, std::vector<char>(band ? 0 : NP, 0));
-            for (int i = 0; !band && i < NP; ++i) {
-                nzi[i][i] = 1;
-                const std::vector<int> rc = rowcols(i);
-                for (int j = 0; j < i; ++j)
-                    for (int k : rc)
-                        if (k >= j && nzi[k][j]) { nzi[i][j] = 1; break; }
-            }
-            // band mode visits the columns in update order (the halves of every dissection level side by
-            // side), so they are factored and substituted concurrently
-            for (int cq = 0; cq < NP; ++cq) {
-                const int c = band ? pl.uord[cq] : cq;
-                if (split && own[c] >= 0 && own[c] != p->part_rank) continue;   // another rank's subtree
-                cur = (split && own[c] < 0) ? &LB : &LA;
-                std::vector<int> rcc;
-                for (int pp : rowcols(c))
-                    if (same_part(pp, own[c])) rcc.push_back(pp);
-                std::vector<int> rows(1, c);
-                rows.insert(rows.end(), pl.colrows[c].begin(), pl.colrows[c].end());
-                for (int i : rows) {   // factor tiles of column c (the diagonal first)
-                    // lookahead over k = c - 1 when tile (c, k) exists and k is the last update of A(c, c)
-                    // in update order (then every copy of a tile sees the same update order)
-                    // and only in dense mode, on a short list of its own: a lookahead task applies 5 tile products
-                    // per entry instead of 2.  A band-mode solve has thousands of tasks on 512 workgroups, so the
-                    // redundant products of column k cost more than the hand-off they save (config 2's solve
-                    // 465 -> 357 us, config 4's 3.25 -> 2.25 ms without them, profiles/r8p_ab_lookahead.txt);
-                    // config 1's few tasks (dense mode, lists <= 16) keep it: it is their chain.  (The band
-                    // kernel, k_chol_flow_band, has no lookahead path.)
-                    const int k = c - 1;
-                    bool la = k >= 0 && pl.nz(c, k) && same_part(k, own[c]) && !band &&
-                              (int)rcc.size() <= LBA_CF_LA_MAX_LIST;
-                    for (int pp : rcc)
-                        if (la && pp != k && rank[pp] > rank[k]) la = false;
-                    const int tcc = pl.tile_id(c, c), tic = i == c ? -1 : pl.tile_id(i, c);
-                    if (la) {
-                        const int tik = pl.tile_id(i, k);
-                        add_task(c, i, 0, 1, tcc, tic, pl.tile_id(k, k), pl.tile_id(c, k), i == c ? -1 : tik);
-                        // updates of the held tiles A(c,c), A(i,c), A(k,k), A(c,k), A(i,k) from panels p < k
-                        std::vector<int> ps;
-                        for (int pp : rcc) if (pp < k) ps.push_back(pp);
-                        for (int pp : rowcols(k))
-                            if (same_part(pp, own[c])) ps.push_back(pp);
-                        std::sort(ps.begin(), ps.end());
-                        ps.erase(std::unique(ps.begin(), ps.end()), ps.end());
-                        std::sort(ps.begin(), ps.end(), by_rank);
-                        // column k is factored as soon as its own updates are in: bit 27 marks the last entry that
-                        // updates row k (entries after it update rows c / i only, e.g. the other half's panels in a
-                        // separator's first column); no such entry: before the first one (task bit 29)
-                        int klast = -1;
-                        for (int pp : ps) {   // only panels that update a held tile; row i only where used
-                            const int tcp = pl.tile_id(c, pp), tkp = pl.tile_id(k, pp), tip = pl.tile_id(i, pp);
-                            const bool fj = tcp >= 0, fk = tkp >= 0, fi = i != c && tip >= 0 && (fj || fk);
-                            if (fk) klast = (int)cur->plist.size();
-                            if (fj || fk) add_entry(pp | (fi << 24) | (fj << 25) | (fk << 26), tcp, fi ? tip : -1, tkp);
-                        }
-                        if (klast >= 0) cur->plist[klast] |= 1 << 27;
-                        else cur->tasks.back() |= 1 << 29;
-                    } else {
-                        add_task(c, i, 0, 0, tcc, tic, -1, -1, -1);
-                        std::vector<int> ps(rcc);
-                        std::sort(ps.begin(), ps.end(), by_rank);
-                        for (int pp : ps) {
-                            const int tip = i == c ? -1 : pl.tile_id(i, pp);
-                            add_entry(pp | ((tip >= 0) << 24), pl.tile_id(c, pp), tip, -1);
-                        }
-                    }
-                    end_task();
-                }
-                if (band) {   // forward substitution y_c = L_cc^-1 (b_c - sum_k L(c,k) y_k), k in update order
-                    add_task(c, c, 4, 0, pl.tile_id(c, c), -1, -1, -1, -1);
-                    std::vector<int> ks(rcc);
-                    std::sort(ks.begin(), ks.end(), by_rank);
-                    for (int kk : ks) add_entry(kk, pl.tile_id(c, kk), -1, -1);
-                    end_task();
-                    continue;
-                }
-                for (int j = 0; j < c; ++j) {    // L^-1 tiles of row c: terms k ascending
-                    if (!nzi[c][j]) continue;
-                    add_task(j, c, 1, 0, -1, -1, -1, -1, -1);
-                    for (int kk : rcc)
-                        if (kk >= j && nzi[kk][j]) add_entry(kk, pl.tile_id(c, kk), -1, -1);
-                    end_task();
-                }
-                if (c == NP - 1) {
-                    // the last panel: y_c = L_cc^-1 (b_c - sum_k L(c,k) y_k) as a substitution task (kind 4): every
-                    // y_k is out well before L_cc is, so y_c follows L_cc^-T at once instead of waiting for the
-                    // L^-1 tiles of the last row and their shares
-                    add_task(c, c, 4, 0, pl.tile_id(c, c), -1, -1, -1, -1);
-                    std::vector<int> ks(rcc);
-                    std::sort(ks.begin(), ks.end(), by_rank);
-                    for (int kk : ks) add_entry(kk, pl.tile_id(c, kk), -1, -1);
-                    end_task();
-                    continue;
-                }
-                add_task(c, c, 3, 0, -1, -1, -1, -1, -1);   // y_c: the nonzero tiles of row c of L^-1
-                for (int kk = 0; kk <= c; ++kk)
-                    if (nzi[c][kk]) add_entry(kk, -1, -1, -1);
-                end_task();
-            }
-            if (split) {
-                // this rank's contributions to the top: per top tile (i, j) the sum over its subtree panels p of
-                // L(i,p) L(j,p)^T, per top panel i the sum of L(i,p) y_p (kinds 6, 7)
-                cur = &LA;
-                for (int j = 0; j < NP; ++j) {
-                    if (own[j] >= 0) continue;
-                    std::vector<int> rows(1, j);
-                    rows.insert(rows.end(), pl.colrows[j].begin(), pl.colrows[j].end());
-                    for (int i : rows) {
-                        std::vector<int> ps;
-                        for (int pp : rowcols(j))
-                            if (own[pp] == p->part_rank && pl.nz(i, pp)) ps.push_back(pp);
-                        if (ps.empty()) continue;
-                        std::sort(ps.begin(), ps.end(), by_rank);
-                        add_task(j, i, 6, 0, pl.tile_id(i, j), -1, -1, -1, -1);
-                        for (int pp : ps) add_entry(pp, pl.tile_id(j, pp), pl.tile_id(i, pp), -1);
-                        end_task();
-                    }
-                    std::vector<int> ks;
-                    for (int pp : rowcols(j))
-                        if (own[pp] == p->part_rank) ks.push_back(pp);
-                    if (ks.empty()) continue;
-                    std::sort(ks.begin(), ks.end(), by_rank);
-                    add_task(j, j, 7, 0, -1, -1, -1, -1, -1);
-                    for (int pp : ks) add_entry(pp, pl.tile_id(j, pp), -1, -1);
-                    end_task();
-                }
-                cur = &LB;
-            }
-            if (band) {
-                // back substitution x_j = L_jj^-T (y_j - sum_i L(i,j)^T x_i) over the rows i > j of column j,
-                // columns in reverse update order, terms in the order their x_i complete
-                for (int cq = NP - 1; cq >= 0; --cq) {
-                    const int j = pl.uord[cq];
-                    if (split && own[j] >= 0 && own[j] != p->part_rank) continue;
-                    add_task(j, j, 5, 0, -1, -1, -1, -1, -1);
-                    std::vector<int> is(pl.colrows[j]);
-                    std::sort(is.begin(), is.end(), [&](int x, int y) { return rank[x] > rank[y]; });
-                    for (int i : is) add_entry(i, pl.tile_id(i, j), -1, -1);
-                    end_task();
-                }
-            }
-            for (int j = 0; !band && j < NP; ++j) {      // solution blocks: rows i >= j of column j of L^-1
-                add_task(j, j, 2, 0, -1, -1, -1, -1, -1);
-                for (int i = j; i < NP; ++i)
-                    if (nzi[i][j]) add_entry(i, -1, -1, -1);
-                end_task();
-            }
-            if (NP >= (1 << 24)) throw ApiError{LBA_E_LIMIT, "internal: too many panels for the dataflow factorisation"};
-            D.cf_tasks = dupload(p, tasks);
-            D.cf_task_i = dupload(p, task_i);
-            D.cf_task_t = dupload(p, task_t);
-            D.cf_ntasks = (int)tasks.size();
-            D.cf_split = split ? 1 : 0;
-            D.cf_ntasks2 = 0;
-            if (split) {
-                D.cf_tasks2 = dupload(p, LB.tasks);
-                D.cf_task_i2 = dupload(p, LB.task_i);
-                D.cf_task_t2 = dupload(p, LB.task_t);
-                D.cf_pl02 = dupload(p, LB.pl0);
-                D.cf_plist2 = dupload(p, LB.plist);
-                D.cf_plist_t2 = dupload(p, LB.plist_t);
-                D.cf_ntasks2 = (int)LB.tasks.size();
-                p->split_tasks[0] = D.cf_ntasks;
-                p->split_tasks[1] = D.cf_ntasks2;
-            }
-            // band mode: no L^-1 tiles (ivready unused: x_j goes to the back tasks as granules, cf_xg)
-            const size_t niv = band ? (size_t)NP + 1 : (size_t)std::max(NP * (NP + 1) / 2, 1);
-            D.cf_linv = band ? nullptr : dalloc<double>(p, (size_t)npad * npad);
-            D.cf_ivready = dalloc<int>(p, niv);
-            zero_later(p, D.cf_ivready, sizeof(int) * niv);
-            D.cf_xg = band ? dalloc<unsigned long long>(p, 2 * (size_t)npad) : nullptr;
-            if (band) zero_later(p, D.cf_xg, sizeof(unsigned long long) * 2 * (size_t)npad);
-            D.cf_pl0 = dupload(p, pl0);
-            D.cf_plist = dupload(p, plist);
-            D.cf_plist_t = dupload(p, plist_t);
-            D.cf_lready = dalloc<int>(p, std::max(ntile, 1));
-            D.cf_dready = dalloc<int>(p, std::max(NP, 1));
-            D.cf_fready = dalloc<int>(p, std::max(NP, 1));
-            zero_later(p, D.cf_fready, sizeof(int) * std::max(NP, 1));
-            D.cf_zready = dalloc<int>(p, std::max(NP, 1));
-            zero_later(p, D.cf_zready, sizeof(int) * std::max(NP, 1));
-            D.cf_zv = band ? nullptr : dalloc<double>(p, std::max((size_t)NP * NP * CHOL_NB, (size_t)1));
-            D.cf_head = dalloc<unsigned long long>(p, 2);   // (ticket counters of the split's two launches)
-            D.cf_abort = dalloc<int>(p, 1);
-            zero_later(p, D.cf_lready, sizeof(int) * std::max(ntile, 1));
-            zero_later(p, D.cf_dready, sizeof(int) * std::max(NP, 1));
-            zero_later(p, D.cf_head, 2 * sizeof(unsigned long long));
-            zero_later(p, D.cf_abort, sizeof(int));
-        }
-        sub("  flow tasks");
-        D.cf_rowptr = dupload(p, pl.rowptr);
-        D.cf_cols = dupload(p, pl.cols);
-        D.ppos = dupload(p, ppos);
-        D.pnat = dupload(p, pnat);
-        D.rpos = dupload(p, rpos);
-        D.rnat = dupload(p, rnat);
-        // every trial, k_lin_schur zeroes S (the tiles of L: structural non-zeros and fill-in) and k_assemble
-        // then writes the structurally non-zero blocks
-        // (in decreasing order of the slots a block sums: the blocks outnumber k_assemble's resident workgroups
-        // and the diagonal blocks sum the most partials, so they go first, as k_lin_schur's tiles do)
-        std::vector<int> asm_list;
-        for (int u = 0; u < n_ublocks; ++u)
-            if (hcnt[u] > 0 || scnt[u] > 0 || ub_i[u] == ub_j[u]) asm_list.push_back(u);
-        if (!std::getenv("LBA_DISPATCH_INDEX_ORDER"))
-            std::stable_sort(asm_list.begin(), asm_list.end(),
-                             [&](int x, int y) { return hcnt[x] + scnt[x] > hcnt[y] + scnt[y]; });
-        D.n_ztiles = ntile;
-        D.part_rank = p->part_rank;
-        D.part_n = p->part_n;
-        {   // natural row -> the rank that adds its once-per-system terms (-1: rank 0)
-            std::vector<int> row_own(npad);
-            for (int r = 0; r < npad; ++r) row_own[r] = own[ppos[r / CHOL_NB]];
-            D.row_own = dupload(p, row_own);
-        }
-        std::vector<int> top_tiles;   // (split) the tiles of L in the top columns
-        if (split)
-            for (int i = 0; i < NP; ++i)
-                for (int q = pl.rowptr[i]; q < pl.rowptr[i + 1]; ++q)
-                    if (own[pl.cols[q]] < 0) top_tiles.push_back(q);
-        D.n_top_tiles = (int)top_tiles.size();
-        D.top_tiles = split ? dupload(p, top_tiles) : nullptr;
-        if (p->part_n > 0) {
-            // bS, b_p (replicated solve: S is all-reduced in place; split: the top tiles lead the buffer)
-            D.n_env = (long long)D.n_top_tiles * CHOL_NB * CHOL_NB + npad + p->np;
-            D.env_buf = dalloc<double>(p, (size_t)D.n_env);
-            D.red4 = dalloc<double>(p, RED_N);
-        }
-        D.asm_list = dupload(p, asm_list);
-        D.n_asm = (int)asm_list.size();
+    D.hslab = dalloc<double>(p, (size_t)144 * std::max(S.n_hslots, 1));
+    D.gslab = dalloc<double>(p, (size_t)GS_PITCH * std::max(S.n_gslots, 1));
+    D.sslab = dalloc<double>(p, (size_t)144 * std::max(S.n_sslots, 1));
+    D.gpslab = dalloc<double>(p, (size_t)GS_PITCH * std::max(S.n_gpslots, 1));
+    D.n_mslots = S.n_mslots; D.n_hslots = S.n_hslots; D.n_gslots = S.n_gslots; D.n_sslots = S.n_sslots; D.n_gpslots = S.n_gpslots;
+}
+
+// per column with m tiles below the diagonal: potrf 32^3/3, m trsm 32^3, the m(m+1)/2 tile updates of the
+// trailing matrix (syrk 32^3 on the diagonal ones, gemm 2 x 32^3 below); summed over the columns j with take(j)
+template <class F>
+double factor_flops(const lba_plan::Plan& pl, F take) {
+    const double b3 = (double)CHOL_NB * CHOL_NB * CHOL_NB;
+    double f = 0.0;
+    for (int j = 0; j < pl.NP; ++j) {
+        if (!take(j)) continue;
+        const double m = (double)pl.colrows[j].size();
+        f += b3 / 3.0 + m * b3 + m * b3 + m * (m - 1.0) * b3;
     }
+    return f;
+}
+
+// ---- device half 2: solve layout of the reduced camera system: dissection order, tile structure of L, task lists
+void solve_layout(lba_problem* p, const Vertices& V, const Slots& S, int npad, SetupClock& clock) {
+    DevProblem& D = p->D;
+    const int n_ublocks = S.n_ublocks;
+    const std::vector<int>&hcnt = S.hcnt, &scnt = S.scnt, &ub_i = S.ub_i, &ub_j = S.ub_j;
+    const int NP = npad / CHOL_NB;
+    // natural tile pattern of S at panel granularity (structural blocks, diagonal), then the nested-
+    // dissection order and the symbolic factorisation (lba_plan.hpp).  Panels holding rows of free
+    // extrinsics (dense: they couple every keyframe) are ordered last.  A partition plans the union
+    // pattern of its ranks' systems.
+    const int NPk = std::min(NP, 12 * V.n_pb_kf / CHOL_NB + (V.n_ext ? 0 : NP));
+    std::vector<std::vector<int>> lower(NP);
+    for (int P = 0; P < NP; ++P) lower[P].push_back(P);
+    std::vector<std::pair<int, int>> edge_panels;   // (this rank's edges' couplings: the split's check)
+    auto couple = [&](int r, int c) {   // natural rows r, c of S
+        const int P = std::max(r, c) / CHOL_NB, Q = std::min(r, c) / CHOL_NB;
+        lower[P].push_back(Q);
+        edge_panels.emplace_back(P, Q);
+    };
+    for (int u = 0; u < n_ublocks; ++u) {
+        if (!(hcnt[u] > 0 || scnt[u] > 0)) continue;
+        const int r0 = 12 * ub_j[u], c0 = 12 * ub_i[u];
+        couple(r0, c0); couple(r0 + 11, c0); couple(r0, c0 + 11); couple(r0 + 11, c0 + 11);
+    }
+    for (int P = 0; P < NP; ++P) {
+        std::sort(lower[P].begin(), lower[P].end());
+        lower[P].erase(std::unique(lower[P].begin(), lower[P].end()), lower[P].end());
+    }
+    if (p->part_n > 0) part_status(p, 0);   // (every rank's preprocessing succeeded, or all throw)
+    if (p->part_n > 0) {   // the union pattern of the ranks' systems (one all-reduce, at set-up)
+        std::vector<double> occ((size_t)NP * NP, 0.0);
+        for (int P = 0; P < NP; ++P)
+            for (int Q : lower[P]) occ[(size_t)P * NP + Q] = 1.0;
+        double* d = dalloc<double>(p, occ.size());
+        HIPCHK(hipMemcpy(d, occ.data(), occ.size() * sizeof(double), hipMemcpyHostToDevice));
+        preduce(p, d, (int64_t)occ.size());
+        HIPCHK(hipStreamSynchronize(p->stream));
+        HIPCHK(hipMemcpy(occ.data(), d, occ.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int P = 0; P < NP; ++P) {
+            lower[P].clear();
+            for (int Q = 0; Q <= P; ++Q)
+                if (occ[(size_t)P * NP + Q] != 0.0 || Q == P) lower[P].push_back(Q);
+        }
+    }
+    clock.sub("  S pattern");
+    const lba_plan::Plan& pl = plan_panels_cached(p->plan_cache, NP, NPk, lower);
+    clock.sub("  dissection plan");
+    p->chain = pl.chain;
+    p->nd_tail = pl.tail;
+    p->nd_levels = pl.levels;
+    // distributed factorisation (LBA_FLAG_SUBTREE_SOLVE, partitioned problems): the elimination tree cut into
+    // one subtree per rank plus the top (lba_plan::split_subtrees, the same on every rank); this rank's
+    // couplings must lie in its subtree and the top (lba_partition_assign gives such a landmark split)
+    const bool split = p->part_n > 0 && (p->cfg.flags & LBA_FLAG_SUBTREE_SOLVE);
+    const std::vector<int> own = split ? lba_plan::split_subtrees(pl, p->part_n) : std::vector<int>(NP, -1);
+    if (split) {   // (a second status point: a rank whose couplings leave its subtree releases its peers)
+        bool stray = false;
+        for (const auto& e : edge_panels) {
+            const int a = own[pl.ppos[e.first]], b = own[pl.ppos[e.second]];
+            if ((a >= 0 && a != p->part_rank) || (b >= 0 && b != p->part_rank)) stray = true;
+        }
+        part_status(p, stray ? 1 : 0);
+        if (stray)
+            throw ApiError{LBA_E_ARG, "partitioned problem: a landmark or edge of rank " +
+                                          std::to_string(p->part_rank) + " couples keyframes of another rank's "
+                                          "subtree (split the window with lba_partition_assign)"};
+    }
+    p->split_own = own;
+    p->ppos_h = pl.ppos;
+    {   // the factorisation work this rank does: its subtree's columns and the top (split), or all of them
+        auto mine = [&](int j) { return own[j] < 0 || own[j] == p->part_rank; };
+        int n_own = 0, n_top = 0;
+        for (int j = 0; j < NP; ++j)
+            if (mine(j)) (own[j] < 0 ? n_top : n_own)++;
+        p->flops_factor_rank = factor_flops(pl, mine);
+        p->split_panels[0] = split ? n_own : 0;
+        p->split_panels[1] = split ? n_top : NP;
+    }
+    p->s_tiles = 0;
+    for (int P = 0; P < NP; ++P) p->s_tiles += (int)lower[P].size();
+    p->flops_factor = factor_flops(pl, [](int) { return true; });
+    const std::vector<int>& ppos = pl.ppos;
+    const std::vector<int>& pnat = pl.pnat;
+    // rows: natural -> factorisation order, and back
+    std::vector<int> rpos(npad), rnat(npad);
+    for (int r = 0; r < npad; ++r) {
+        rpos[r] = ppos[r / CHOL_NB] * CHOL_NB + r % CHOL_NB;
+        rnat[rpos[r]] = r;
+    }
+    // solve path: L^-1 tiles (the solve has no substitution chain, but L^-1 is dense below the
+    // diagonal: O(n^3) work) up to CF_AUTO_BAND_NP panels, substitution tasks above (or when asked)
+    const bool band = split || (!(p->cfg.flags & LBA_FLAG_DENSE_SOLVE) &&
+                                ((p->cfg.flags & LBA_FLAG_BAND_SOLVE) || NP > CF_AUTO_BAND_NP));
+    D.cf_band = band ? 1 : 0;
+    const int ntile = pl.ntile();
+    {   // dataflow factorisation + solve (k_chol_flow): its task lists (lba_plan::flow_tasks) and flags
+        const lba_plan::FlowTasks ft = lba_plan::flow_tasks(pl, band, split, own, p->part_rank);
+        const lba_plan::TaskList &LA = ft.a, &LB = ft.b;
+        if (NP >= (1 << 24)) throw ApiError{LBA_E_LIMIT, "internal: too many panels for the dataflow factorisation"};
+        D.cf_tasks = dupload(p, LA.tasks);
+        D.cf_task_i = dupload(p, LA.task_i);
+        D.cf_task_t = dupload(p, LA.task_t);
+        D.cf_ntasks = (int)LA.tasks.size();
+        D.cf_split = split ? 1 : 0;
+        D.cf_ntasks2 = 0;
+        if (split) {
+            D.cf_tasks2 = dupload(p, LB.tasks);
+            D.cf_task_i2 = dupload(p, LB.task_i);
+            D.cf_task_t2 = dupload(p, LB.task_t);
+            D.cf_pl02 = dupload(p, LB.pl0);
+            D.cf_plist2 = dupload(p, LB.plist);
+            D.cf_plist_t2 = dupload(p, LB.plist_t);
+            D.cf_ntasks2 = (int)LB.tasks.size();
+            p->split_tasks[0] = D.cf_ntasks;
+            p->split_tasks[1] = D.cf_ntasks2;
+        }
+        // band mode: no L^-1 tiles (ivready unused: x_j goes to the back tasks as granules, cf_xg)
+        const size_t niv = band ? (size_t)NP + 1 : (size_t)std::max(NP * (NP + 1) / 2, 1);
+        D.cf_linv = band ? nullptr : dalloc<double>(p, (size_t)npad * npad);
+        D.cf_ivready = dalloc<int>(p, niv);
+        zero_later(p, D.cf_ivready, sizeof(int) * niv);
+        D.cf_xg = band ? dalloc<unsigned long long>(p, 2 * (size_t)npad) : nullptr;
+        if (band) zero_later(p, D.cf_xg, sizeof(unsigned long long) * 2 * (size_t)npad);
+        D.cf_pl0 = dupload(p, LA.pl0);
+        D.cf_plist = dupload(p, LA.plist);
+        D.cf_plist_t = dupload(p, LA.plist_t);
+        D.cf_lready = dalloc<int>(p, std::max(ntile, 1));
+        D.cf_dready = dalloc<int>(p, std::max(NP, 1));
+        D.cf_fready = dalloc<int>(p, std::max(NP, 1));
+        zero_later(p, D.cf_fready, sizeof(int) * std::max(NP, 1));
+        D.cf_zready = dalloc<int>(p, std::max(NP, 1));
+        zero_later(p, D.cf_zready, sizeof(int) * std::max(NP, 1));
+        D.cf_zv = band ? nullptr : dalloc<double>(p, std::max((size_t)NP * NP * CHOL_NB, (size_t)1));
+        D.cf_head = dalloc<unsigned long long>(p, 2);   // (ticket counters of the split's two launches)
+        D.cf_abort = dalloc<int>(p, 1);
+        zero_later(p, D.cf_lready, sizeof(int) * std::max(ntile, 1));
+        zero_later(p, D.cf_dready, sizeof(int) * std::max(NP, 1));
+        zero_later(p, D.cf_head, 2 * sizeof(unsigned long long));
+        zero_later(p, D.cf_abort, sizeof(int));
+    }
+    clock.sub("  flow tasks");
+    D.cf_rowptr = dupload(p, pl.rowptr);
+    D.cf_cols = dupload(p, pl.cols);
+    D.ppos = dupload(p, ppos);
+    D.pnat = dupload(p, pnat);
+    D.rpos = dupload(p, rpos);
+    D.rnat = dupload(p, rnat);
+    // every trial, k_lin_schur zeroes S (the tiles of L: structural non-zeros and fill-in) and k_assemble
+    // then writes the structurally non-zero blocks
+    // (in decreasing order of the slots a block sums: the blocks outnumber k_assemble's resident workgroups
+    // and the diagonal blocks sum the most partials, so they go first, as k_lin_schur's tiles do)
+    std::vector<int> asm_list;
+    for (int u = 0; u < n_ublocks; ++u)
+        if (hcnt[u] > 0 || scnt[u] > 0 || ub_i[u] == ub_j[u]) asm_list.push_back(u);
+    if (!std::getenv("LBA_DISPATCH_INDEX_ORDER"))
+        std::stable_sort(asm_list.begin(), asm_list.end(),
+                         [&](int x, int y) { return hcnt[x] + scnt[x] > hcnt[y] + scnt[y]; });
+    D.n_ztiles = ntile;
+    D.part_rank = p->part_rank;
+    D.part_n = p->part_n;
+    {   // natural row -> the rank that adds its once-per-system terms (-1: rank 0)
+        std::vector<int> row_own(npad);
+        for (int r = 0; r < npad; ++r) row_own[r] = own[ppos[r / CHOL_NB]];
+        D.row_own = dupload(p, row_own);
+    }
+    std::vector<int> top_tiles;   // (split) the tiles of L in the top columns
+    if (split)
+        for (int i = 0; i < NP; ++i)
+            for (int q = pl.rowptr[i]; q < pl.rowptr[i + 1]; ++q)
+                if (own[pl.cols[q]] < 0) top_tiles.push_back(q);
+    D.n_top_tiles = (int)top_tiles.size();
+    D.top_tiles = split ? dupload(p, top_tiles) : nullptr;
+    if (p->part_n > 0) {
+        // bS, b_p (replicated solve: S is all-reduced in place; split: the top tiles lead the buffer)
+        D.n_env = (long long)D.n_top_tiles * CHOL_NB * CHOL_NB + npad + p->np;
+        D.env_buf = dalloc<double>(p, (size_t)D.n_env);
+        D.red4 = dalloc<double>(p, RED_N);
+    }
+    D.asm_list = dupload(p, asm_list);
+    D.n_asm = (int)asm_list.size();
+}
+
+// ---- device half 3: the solver, flag and state buffers
+void solver_buffers(lba_problem* p, const Window& W, const Vertices& V, const GpSamples& G, const LmOrder& L,
+                    const Tiles& T, const Slots& S, const DevOrder& O, int npad, SetupClock& clock) {
+    DevProblem& D = p->D;
+    const int n_obs = W.n_obs, n_kfs = V.n_kfs, n_ext = V.n_ext, nl = L.nl, n_seg = T.n_seg, n_heavy = (int)T.hv_lm.size();
     D.npad = npad;
     // S and L: packed envelope tiles (memory O(envelope); the natural-order dense H_pp of lba_linearize
     // goes to Sfull, allocated on first use)
     const size_t n_env_doubles = (size_t)D.n_ztiles * CHOL_NB * CHOL_NB;
     p->s_bytes = 2 * n_env_doubles * sizeof(double);
-    sub("  envelope + assembly lists");
+    clock.sub("  envelope + assembly lists");
     D.Lm = dalloc<double>(p, n_env_doubles + 1);
     D.LinvT = dalloc<double>(p, (size_t)npad * CHOL_NB + 1);
     // Hpl: only the heavy landmarks' canonical pairs, then the segment pairs (regular tiles keep theirs in LDS)
-    D.hpl_base = lm_pair0[n_reg];
-    D.n_hpl = n_pairs - D.hpl_base + n_segpairs;
+    D.hpl_base = L.lm_pair0[L.n_reg];
+    D.n_hpl = L.n_pairs - D.hpl_base + T.n_segpairs;
     D.Hpl = dalloc<double>(p, (size_t)36 * std::max(D.n_hpl, 1));
     D.Hll = dalloc<double>(p, (size_t)9 * std::max(nl + n_seg, 1));               // landmarks, then segments
     D.n_lm_all = nl + n_seg;
@@ -2149,12 +844,12 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
     zero_later(p, D.xsol, sizeof(double) * (npad + 1));
     D.x = dalloc<double>(p, p->np + 3 * (size_t)nl + 1);
     zero_later(p, D.x, sizeof(double) * (p->np + 3 * (size_t)nl + 1));   // BlockSolver::_x before any solve
-    const int nchi = n_tiles + D.n_prior + D.n_vel + D.n_eprior;
+    const int nchi = T.n_tiles() + D.n_prior + D.n_vel + D.n_eprior;
     D.chi_lin = dalloc<double>(p, nchi + 1);
     D.n_chi = nchi;
     D.chi_eval = dalloc<double>(p, nchi + 1);
     // k_update: one workgroup per GP pair, KFs at 64 per workgroup, one per regular tile, heavy landmarks at 64
-    D.n_upd_blocks = D.n_gp + (n_kfs + 63) / 64 + n_stiles + (n_heavy + 63) / 64;
+    D.n_upd_blocks = D.n_gp + (n_kfs + 63) / 64 + T.n_stiles + (n_heavy + 63) / 64;
     if (D.n_upd_blocks == 0) D.n_upd_blocks = 1;
     D.scale_part = dalloc<double>(p, D.n_upd_blocks);
     // the trial evaluation fused into k_update (LBA_NO_FUSED_EVAL: k_eval after it): not with heavy landmarks (their
@@ -2182,7 +877,7 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
         const int nkb = (n_kfs + UPD_BLOCK_KFS - 1) / UPD_BLOCK_KFS;
         std::vector<int> prod(std::max(D.n_smp, 1), -1);
         for (int g = 0; g < D.n_gp; ++g)
-            for (int s = gp_s0[g]; s < gp_s0[g + 1]; ++s) prod[s] = g;
+            for (int s = G.gp_s0[g]; s < G.gp_s0[g + 1]; ++s) prod[s] = g;
         for (int k = 0; k < n_kfs; ++k) prod[D.n_gps + k] = D.n_gp + k / UPD_BLOCK_KFS;
         D.smp_prod = dupload(p, prod);
         D.upd_flag = dalloc<int>(p, (size_t)FLAG_STRIDE * (D.n_gp + nkb + 1));
@@ -2192,8 +887,8 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
     // k_expand + k_assemble of a trial in one launch (LBA_NO_FUSED_ASM: two): not with heavy landmarks (their merge
     // is k_expand's), partitioned problems or the fused factorisation flow (which assembles S itself)
     D.fuse_asm = (n_heavy == 0 && p->part_n == 0 && std::getenv("LBA_NO_FUSED_ASM") == nullptr) ? 1 : 0;
-    D.hs_prod = dupload(p, hs_prod);
-    D.gs_prod = dupload(p, gs_prod);
+    D.hs_prod = dupload(p, S.hs_prod);
+    D.gs_prod = dupload(p, S.gs_prod);
     D.exp_flag = dalloc<int>(p, (size_t)FLAG_STRIDE * std::max(D.n_smp, 1));
     zero_later(p, D.exp_flag, sizeof(int) * FLAG_STRIDE * std::max(D.n_smp, 1));
     p->asm_epoch = 0;
@@ -2207,14 +902,83 @@ int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xy
     D.depth_ok = dalloc<unsigned char>(p, std::max(n_obs, 1));
     zero_later(p, D.info, sizeof(int));
     for (int s = 0; s < 2; ++s) {
-        p->kst[s] = dalloc<double>(p, kst.size());
-        p->lst[s] = dalloc<double>(p, lst.size());
-        upload_into(p, p->kst[s], kst);
-        upload_into(p, p->lst[s], lst);
+        p->kst[s] = dalloc<double>(p, O.kst.size());
+        p->lst[s] = dalloc<double>(p, O.lst.size());
+        upload_into(p, p->kst[s], O.kst);
+        upload_into(p, p->lst[s], O.lst);
         D.kbuf[s] = p->kst[s];
         D.lbuf[s] = p->lst[s];
     }
     zero_later(p, D.ctl, sizeof(LMCtl));
+}
+
+int set_problem(lba_problem* p, const lba_kf* kfs, int n_kf, const double* lm_xyz, int n_lm, const lba_obs* obs,
+                int n_obs, const lba_prior* priors, int n_priors, const int32_t* vel_kfs, int n_vel,
+                const lba_cam* cams, int n_cam) {
+    if (n_kf < 0 || n_lm < 0 || n_obs < 0 || n_priors < 0 || n_vel < 0 || n_cam < 0)
+        throw ApiError{LBA_E_ARG, "negative array size"};
+    if ((n_kf && !kfs) || (n_lm && !lm_xyz) || (n_obs && !obs) || (n_priors && !priors) || (n_vel && !vel_kfs) ||
+        (n_cam && !cams))
+        throw ApiError{LBA_E_ARG, "null array with non-zero size"};
+    const Window W{kfs, n_kf, lm_xyz, n_lm, obs, n_obs, priors, n_priors, vel_kfs, n_vel, cams, n_cam};
+    SetupScratch& scr = p->scr;
+    const Checks C = validate_window(W, p->part_n > 0, scr);
+
+    SetupClock clock(std::getenv("LBA_SETUP_TIMING") != nullptr);
+    p->setup_ms.clear();
+    auto mark = [&](const char* what) {
+        if (p->stream) flush_uploads(p);   // (the arrays staged in this phase go out while the next one runs)
+        p->setup_ms.push_back(clock.phase(what));
+    };
+    p->status_entered = false;
+    if (p->stream) HIPCHK(hipStreamSynchronize(p->stream));   // (the buffers are reused below)
+    free_all(p);
+    p->zero_list.clear();
+    p->n_kf = n_kf; p->n_lm = n_lm; p->n_obs = n_obs; p->n_cam = n_cam;
+    p->lm_host.assign(lm_xyz, lm_xyz + 3 * (size_t)n_lm);
+    p->kf_fixed.resize(n_kf);
+    for (int k = 0; k < n_kf; ++k) p->kf_fixed[k] = kfs[k].fixed != 0;
+
+    // ---- the host stages (lba_setup.hpp)
+    StageWork wk;
+    const Vertices V = number_vertices(W, C, p->part_n > 0, scr, wk);
+    p->kf_hidx = V.kf_hidx;
+    p->n_ext = V.n_ext;
+    p->ext_cams = C.ext_cams;
+    p->cams.assign(cams, cams + n_cam);
+    p->n_pb = V.n_pb;
+    p->np = V.np;
+    p->np_ext = V.np_ext;
+    p->pose_ext = V.pose_ext;
+    if ((p->cfg.flags & LBA_FLAG_DENSE_SOLVE) && p->np > CF_DENSE_MAX_NP * CHOL_NB)
+        throw ApiError{LBA_E_LIMIT, "the L^-1-tile solve is limited to pose systems of 6144"};
+    clock.sub("checks + activity");
+    const GpSamples G = number_gp(W, V, clock, scr, wk);
+    const LmOrder L = order_landmarks(W, V, G, clock, scr, wk);
+    p->n_lm_dev = L.nl;
+    p->lm_orig = L.order;
+    lm_dev_of(L, n_lm, p->lm_dev);
+    mark("order/pairs");
+    const Tiles T = build_tiles(W, V, G, L, clock, scr);
+    mark("tiles");
+    const Slots S = build_slots(W, V, G, L, T, wk);
+    clock.sub("slab slots");
+    const DevOrder O = device_order(W, C, V, L, p->lm_dev, clock, scr, p->obs_dev);
+    mark("slots/state");
+    if (p->host_only) {   // (lba_setup_host_profile)
+        const Fingerprint F = layout_fingerprint(T, S, scr);
+        p->setup_hash = F.hash;
+        p->setup_tiles = F.n_tiles;
+        std::copy(F.shapes, F.shapes + LBA_TILE_SHAPES, p->setup_shapes);
+        return LBA_OK;
+    }
+
+    // ---- the device half
+    upload_window(p, W, V, G, L, T, S, O);
+    const int npad = (p->np + CHOL_NB - 1) / CHOL_NB * CHOL_NB;
+    mark("upload");
+    solve_layout(p, V, S, npad, clock);
+    solver_buffers(p, W, V, G, L, T, S, O, npad, clock);
     flush_zero_ranges(p);
     flush_uploads(p);
     HIPCHK(hipStreamSynchronize(p->stream));   // the staged uploads (dupload) have landed, the ranges are zero

@@ -462,4 +462,193 @@ inline std::vector<int> split_subtrees(const Plan& pl, int nranks) {
     return own;
 }
 
+// One launch's task list of the dataflow factorisation + solve (k_chol_flow).  Task t: (j, i, kind) with five tile
+// ids (task_t) and the update / term entries plist[pl0[t] .. pl0[t + 1]) with three tile ids each (plist_t).
+struct TaskList {
+    std::vector<int> tasks, task_i, task_t, pl0{0}, plist, plist_t;
+};
+struct FlowTasks {
+    TaskList a, b;   // launch 0; launch 1 (split only)
+};
+
+#ifndef LBA_CF_LA_MAX_LIST   // (A/B builds only, scripts/exp_build.sh)
+#define LBA_CF_LA_MAX_LIST 16
+#endif
+
+// The tasks of a plan in topological order: per column c the factor tiles of its rows (the diagonal first), then
+// (L^-1 solve) the L^-1 tiles of row c; at the end one solution task per panel.  band: substitution tasks instead
+// of L^-1 tiles.
+// Distributed factorisation (split; own = split_subtrees, me = this rank): list a (launch 0) holds this rank's
+// subtree columns and its contributions to the top, list b (launch 1) the top columns (updated from top panels
+// only: the subtrees' updates are summed into the top tiles between the launches) and the back substitution of
+// the top and this rank's columns.  Unsplit: everything in list a, b empty.
+inline FlowTasks flow_tasks(const Plan& pl, bool band, bool split, const std::vector<int>& own, int me) {
+    const int NP = pl.NP;
+    FlowTasks out;
+    TaskList &LA = out.a, &LB = out.b;
+    TaskList* cur = &LA;
+    auto add_task = [&](int j, int i, int kind, int la, int t0, int t1, int t2, int t3, int t4) {
+        cur->tasks.push_back(j | (kind << 24) | (la << 28));
+        cur->task_i.push_back(i);
+        cur->task_t.push_back(t0); cur->task_t.push_back(t1); cur->task_t.push_back(t2); cur->task_t.push_back(t3);
+        cur->task_t.push_back(t4);
+    };
+    auto add_entry = [&](int e, int t0, int t1, int t2) {
+        cur->plist.push_back(e);
+        cur->plist_t.push_back(t0); cur->plist_t.push_back(t1); cur->plist_t.push_back(t2);
+    };
+    auto end_task = [&]() { cur->pl0.push_back((int)cur->plist.size()); };
+    // (split) the panels whose updates a column of owner o takes inside its launch: its own subtree's, or the
+    // top's for a top column
+    auto same_part = [&](int pp, int o) { return !split || own[pp] == o; };
+    const std::vector<int>& rank = pl.rank;
+    auto by_rank = [&](int x, int y) { return rank[x] < rank[y]; };
+    // row c's columns below the diagonal
+    auto rowcols = [&](int c) {
+        return std::vector<int>(pl.cols.begin() + pl.rowptr[c], pl.cols.begin() + pl.rowptr[c + 1] - 1);
+    };
+    // structure of L^-1 (L^-1 solve only): Linv(i,j) != 0 iff some k in [j, i) with L(i,k) != 0 has
+    // Linv(k,j) != 0
+    std::vector<std::vector<char>> nzi(band ? 0 : NP, std::vector<char>(band ? 0 : NP, 0));
+    for (int i = 0; !band && i < NP; ++i) {
+        nzi[i][i] = 1;
+        const std::vector<int> rc = rowcols(i);
+        for (int j = 0; j < i; ++j)
+            for (int k : rc)
+                if (k >= j && nzi[k][j]) { nzi[i][j] = 1; break; }
+    }
+    // band mode visits the columns in update order (the halves of every dissection level side by
+    // side), so they are factored and substituted concurrently
+    for (int cq = 0; cq < NP; ++cq) {
+        const int c = band ? pl.uord[cq] : cq;
+        if (split && own[c] >= 0 && own[c] != me) continue;   // another rank's subtree
+        cur = (split && own[c] < 0) ? &LB : &LA;
+        std::vector<int> rcc;
+        for (int pp : rowcols(c))
+            if (same_part(pp, own[c])) rcc.push_back(pp);
+        std::vector<int> rows(1, c);
+        rows.insert(rows.end(), pl.colrows[c].begin(), pl.colrows[c].end());
+        for (int i : rows) {   // factor tiles of column c (the diagonal first)
+            // lookahead over k = c - 1 when tile (c, k) exists and k is the last update of A(c, c)
+            // in update order (then every copy of a tile sees the same update order)
+            // and only in dense mode, on a short list of its own: a lookahead task applies 5 tile products
+            // per entry instead of 2.  A band-mode solve has thousands of tasks on 512 workgroups, so the
+            // redundant products of column k cost more than the hand-off they save (config 2's solve
+            // 465 -> 357 us, config 4's 3.25 -> 2.25 ms without them, profiles/r8p_ab_lookahead.txt);
+            // config 1's few tasks (dense mode, lists <= 16) keep it: it is their chain.  (The band
+            // kernel, k_chol_flow_band, has no lookahead path.)
+            const int k = c - 1;
+            bool la = k >= 0 && pl.nz(c, k) && same_part(k, own[c]) && !band &&
+                      (int)rcc.size() <= LBA_CF_LA_MAX_LIST;
+            for (int pp : rcc)
+                if (la && pp != k && rank[pp] > rank[k]) la = false;
+            const int tcc = pl.tile_id(c, c), tic = i == c ? -1 : pl.tile_id(i, c);
+            if (la) {
+                const int tik = pl.tile_id(i, k);
+                add_task(c, i, 0, 1, tcc, tic, pl.tile_id(k, k), pl.tile_id(c, k), i == c ? -1 : tik);
+                // updates of the held tiles A(c,c), A(i,c), A(k,k), A(c,k), A(i,k) from panels p < k
+                std::vector<int> ps;
+                for (int pp : rcc) if (pp < k) ps.push_back(pp);
+                for (int pp : rowcols(k))
+                    if (same_part(pp, own[c])) ps.push_back(pp);
+                std::sort(ps.begin(), ps.end());
+                ps.erase(std::unique(ps.begin(), ps.end()), ps.end());
+                std::sort(ps.begin(), ps.end(), by_rank);
+                // column k is factored as soon as its own updates are in: bit 27 marks the last entry that
+                // updates row k (entries after it update rows c / i only, e.g. the other half's panels in a
+                // separator's first column); no such entry: before the first one (task bit 29)
+                int klast = -1;
+                for (int pp : ps) {   // only panels that update a held tile; row i only where used
+                    const int tcp = pl.tile_id(c, pp), tkp = pl.tile_id(k, pp), tip = pl.tile_id(i, pp);
+                    const bool fj = tcp >= 0, fk = tkp >= 0, fi = i != c && tip >= 0 && (fj || fk);
+                    if (fk) klast = (int)cur->plist.size();
+                    if (fj || fk) add_entry(pp | (fi << 24) | (fj << 25) | (fk << 26), tcp, fi ? tip : -1, tkp);
+                }
+                if (klast >= 0) cur->plist[klast] |= 1 << 27;
+                else cur->tasks.back() |= 1 << 29;
+            } else {
+                add_task(c, i, 0, 0, tcc, tic, -1, -1, -1);
+                std::vector<int> ps(rcc);
+                std::sort(ps.begin(), ps.end(), by_rank);
+                for (int pp : ps) {
+                    const int tip = i == c ? -1 : pl.tile_id(i, pp);
+                    add_entry(pp | ((tip >= 0) << 24), pl.tile_id(c, pp), tip, -1);
+                }
+            }
+            end_task();
+        }
+        for (int j = 0; !band && j < c; ++j) {    // L^-1 tiles of row c: terms k ascending
+            if (!nzi[c][j]) continue;
+            add_task(j, c, 1, 0, -1, -1, -1, -1, -1);
+            for (int kk : rcc)
+                if (kk >= j && nzi[kk][j]) add_entry(kk, pl.tile_id(c, kk), -1, -1);
+            end_task();
+        }
+        // y_c = L_cc^-1 (b_c - sum_k L(c,k) y_k), k in update order, as a substitution task (kind 4): every column
+        // in band mode; in dense mode the last panel, where every y_k is out well before L_cc is, so y_c follows
+        // L_cc^-T at once instead of waiting for the L^-1 tiles of the last row and their shares
+        if (band || c == NP - 1) {
+            add_task(c, c, 4, 0, pl.tile_id(c, c), -1, -1, -1, -1);
+            std::vector<int> ks(rcc);
+            std::sort(ks.begin(), ks.end(), by_rank);
+            for (int kk : ks) add_entry(kk, pl.tile_id(c, kk), -1, -1);
+            end_task();
+            continue;
+        }
+        add_task(c, c, 3, 0, -1, -1, -1, -1, -1);   // y_c: the nonzero tiles of row c of L^-1
+        for (int kk = 0; kk <= c; ++kk)
+            if (nzi[c][kk]) add_entry(kk, -1, -1, -1);
+        end_task();
+    }
+    if (split) {
+        // this rank's contributions to the top: per top tile (i, j) the sum over its subtree panels p of
+        // L(i,p) L(j,p)^T, per top panel i the sum of L(i,p) y_p (kinds 6, 7)
+        cur = &LA;
+        for (int j = 0; j < NP; ++j) {
+            if (own[j] >= 0) continue;
+            std::vector<int> rows(1, j);
+            rows.insert(rows.end(), pl.colrows[j].begin(), pl.colrows[j].end());
+            for (int i : rows) {
+                std::vector<int> ps;
+                for (int pp : rowcols(j))
+                    if (own[pp] == me && pl.nz(i, pp)) ps.push_back(pp);
+                if (ps.empty()) continue;
+                std::sort(ps.begin(), ps.end(), by_rank);
+                add_task(j, i, 6, 0, pl.tile_id(i, j), -1, -1, -1, -1);
+                for (int pp : ps) add_entry(pp, pl.tile_id(j, pp), pl.tile_id(i, pp), -1);
+                end_task();
+            }
+            std::vector<int> ks;
+            for (int pp : rowcols(j))
+                if (own[pp] == me) ks.push_back(pp);
+            if (ks.empty()) continue;
+            std::sort(ks.begin(), ks.end(), by_rank);
+            add_task(j, j, 7, 0, -1, -1, -1, -1, -1);
+            for (int pp : ks) add_entry(pp, pl.tile_id(j, pp), -1, -1);
+            end_task();
+        }
+        cur = &LB;
+    }
+    if (band) {
+        // back substitution x_j = L_jj^-T (y_j - sum_i L(i,j)^T x_i) over the rows i > j of column j,
+        // columns in reverse update order, terms in the order their x_i complete
+        for (int cq = NP - 1; cq >= 0; --cq) {
+            const int j = pl.uord[cq];
+            if (split && own[j] >= 0 && own[j] != me) continue;
+            add_task(j, j, 5, 0, -1, -1, -1, -1, -1);
+            std::vector<int> is(pl.colrows[j]);
+            std::sort(is.begin(), is.end(), [&](int x, int y) { return rank[x] > rank[y]; });
+            for (int i : is) add_entry(i, pl.tile_id(i, j), -1, -1);
+            end_task();
+        }
+    }
+    for (int j = 0; !band && j < NP; ++j) {      // solution blocks: rows i >= j of column j of L^-1
+        add_task(j, j, 2, 0, -1, -1, -1, -1, -1);
+        for (int i = j; i < NP; ++i)
+            if (nzi[i][j]) add_entry(i, -1, -1, -1);
+        end_task();
+    }
+    return out;
+}
+
 }  // namespace lba_plan

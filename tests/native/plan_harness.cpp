@@ -56,4 +56,31 @@ int split_probe(int NP, int NPk, int npairs, const int* pairs, int nranks, int* 
     }
     return pl.ntile();
 }
+
+// k_chol_flow's task lists (lba_plan::flow_tasks) of the same plan: band or L^-1 mode; nranks > 1: the split lists of
+// rank `me` (band mode).  which: 0 list a, 1 list b.  sizes[2] receives the list's tasks and entries; with
+// tasks == nullptr nothing else is written (the size query).  tasks / task_i [nt], task_t [5 nt], pl0 [nt + 1],
+// plist [ne], plist_t [3 ne].
+int flow_probe(int NP, int NPk, int npairs, const int* pairs, int band, int nranks, int me, int which, int* sizes,
+               int* tasks, int* task_i, int* task_t, int* pl0, int* plist, int* plist_t) {
+    const auto lower = lower_of(NP, npairs, pairs);
+    const lba_plan::Plan pl = lba_plan::make_plan(NP, NPk, lower, 64, true, 16, 0);
+    const bool split = nranks > 1;
+    const std::vector<int> own = split ? lba_plan::split_subtrees(pl, nranks) : std::vector<int>(NP, -1);
+    const lba_plan::FlowTasks ft = lba_plan::flow_tasks(pl, split || band != 0, split, own, me);
+    const lba_plan::TaskList& l = which ? ft.b : ft.a;
+    sizes[0] = (int)l.tasks.size();
+    sizes[1] = (int)l.plist.size();
+    if (!tasks) return 0;
+    if (l.task_i.size() != l.tasks.size() || l.task_t.size() != 5 * l.tasks.size() ||
+        l.plist_t.size() != 3 * l.plist.size() || l.pl0.size() != l.tasks.size() + 1)
+        return -1;
+    std::memcpy(tasks, l.tasks.data(), sizeof(int) * l.tasks.size());
+    std::memcpy(task_i, l.task_i.data(), sizeof(int) * l.task_i.size());
+    std::memcpy(task_t, l.task_t.data(), sizeof(int) * l.task_t.size());
+    std::memcpy(pl0, l.pl0.data(), sizeof(int) * l.pl0.size());
+    std::memcpy(plist, l.plist.data(), sizeof(int) * l.plist.size());
+    std::memcpy(plist_t, l.plist_t.data(), sizeof(int) * l.plist_t.size());
+    return 0;
+}
 }

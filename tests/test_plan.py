@@ -121,6 +121,113 @@ def test_extrinsic_panels_last(plan_harness):
         check_plan(NP, pr, pl, NPk=NPk)
 
 
+def flow(h, NP, pairs, band, nranks=1, me=0, which=0):
+    """One task list of lba_plan::flow_tasks for the plan `plan(h, NP, pairs)` makes."""
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    sizes = np.zeros(2, np.int32)
+    args = (NP, NP, len(pr), _p(pr), int(band), nranks, me, which, _p(sizes))
+    assert h.flow_probe(*args, None, None, None, None, None, None) == 0
+    nt, ne = int(sizes[0]), int(sizes[1])
+    tasks, task_i, task_t = np.zeros(nt, np.int32), np.zeros(nt, np.int32), np.zeros((nt, 5), np.int32)
+    pl0, plist, plist_t = np.full(nt + 2, -7, np.int32), np.zeros(ne, np.int32), np.zeros((ne, 3), np.int32)
+    assert h.flow_probe(*args, _p(tasks), _p(task_i), _p(task_t), _p(pl0), _p(plist), _p(plist_t)) == 0
+    assert pl0[nt + 1] == -7   # pl0 has exactly one more element than tasks (the probe checks its length too)
+    return dict(j=tasks & 0xffffff, kind=(tasks >> 24) & 15, i=task_i, t=task_t, pl0=pl0[:nt + 1], pp=plist & 0xffffff,
+                pt=plist_t)
+
+
+def split_own(h, NP, pairs, nranks):
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    own, parent = np.zeros(NP, np.int32), np.zeros(NP, np.int32)
+    h.split_probe(NP, NP, len(pr), _p(pr), nranks, _p(own), _p(parent))
+    return own
+
+
+def check_lists(lists, ntile):
+    """What holds for the lists of one rank's launches, in launch order: pl0, the tile ids, the diagonal first, and
+    the topological order (an entry's source panel has all its factor tasks earlier)."""
+    for fl in lists:
+        nt = len(fl["j"])
+        assert fl["pl0"][0] == 0 and np.all(np.diff(fl["pl0"]) >= 0) and fl["pl0"][nt] == len(fl["pp"])
+        for ids in (fl["t"], fl["pt"]):
+            assert np.all(ids >= -1) and np.all(ids < ntile)
+    j = np.concatenate([fl["j"] for fl in lists])
+    i = np.concatenate([fl["i"] for fl in lists])
+    kind = np.concatenate([fl["kind"] for fl in lists])
+    entries = []
+    for fl in lists:
+        entries += [fl["pp"][fl["pl0"][t]:fl["pl0"][t + 1]] for t in range(len(fl["j"]))]
+    last_factor, diag_at = {}, {}
+    for t in np.nonzero(kind == 0)[0]:
+        last_factor[int(j[t])] = int(t)
+        if i[t] == j[t]:
+            diag_at.setdefault(int(j[t]), int(t))
+        assert diag_at.get(int(j[t]), t + 1) <= t, (t, j[t], i[t])   # the diagonal task before the off-diagonal ones
+    for t, pps in enumerate(entries):
+        for pp in pps:
+            assert last_factor.get(int(pp), len(j)) < t, (t, int(j[t]), int(i[t]), int(kind[t]), int(pp))
+
+
+FLOW_PATTERNS = {
+    "band8": (8, band_pairs(8, 3)),
+    "band19": (19, band_pairs(19, 5)),
+    "band24": (24, band_pairs(24, 2)),
+    "revisit24": (24, revisit_pairs(24, 3, 2)),
+    "tail20": (20, band_pairs(20, 3) + [(19, 0), (19, 1), (18, 0)]),
+}
+
+
+@pytest.mark.parametrize("band", [0, 1])
+@pytest.mark.parametrize("name", sorted(FLOW_PATTERNS))
+def test_flow_tasks(plan_harness, name, band):
+    """k_chol_flow's task lists (lba_plan::flow_tasks), unsplit, with L^-1 tiles and as a substitution solve."""
+    NP, pr = FLOW_PATTERNS[name]
+    pl = plan(plan_harness, NP, pr)
+    fl = flow(plan_harness, NP, pr, band)
+    assert len(flow(plan_harness, NP, pr, band, which=1)["j"]) == 0   # unsplit: everything in the first list
+    check_lists([fl], pl["ntile"])
+    # every stored tile (i, c) of L is the target of exactly one factor task
+    f = fl["kind"] == 0
+    target = np.where(fl["i"][f] == fl["j"][f], fl["t"][f, 0], fl["t"][f, 1])
+    assert sorted(target.tolist()) == list(range(pl["ntile"]))
+    row_of = np.repeat(np.arange(NP), np.diff(pl["rowptr"]))
+    np.testing.assert_array_equal(row_of[target], fl["i"][f])
+    np.testing.assert_array_equal(pl["cols"][target], fl["j"][f])
+    # one solution per panel: kind 2 (L^-1 tiles) or kind 5 (back substitution)
+    assert sorted(fl["j"][fl["kind"] == (5 if band else 2)].tolist()) == list(range(NP))
+
+
+@pytest.mark.parametrize("me", [0, 1])
+@pytest.mark.parametrize("name", sorted(FLOW_PATTERNS))
+def test_flow_tasks_split(plan_harness, name, me):
+    """The distributed factorisation's two lists on each of 2 ranks."""
+    NP, pr = FLOW_PATTERNS[name]
+    pl = plan(plan_harness, NP, pr)
+    own = split_own(plan_harness, NP, pr, 2)
+    A = flow(plan_harness, NP, pr, 1, nranks=2, me=me, which=0)
+    B = flow(plan_harness, NP, pr, 1, nranks=2, me=me, which=1)
+    check_lists([A, B], pl["ntile"])
+    row_of = np.repeat(np.arange(NP), np.diff(pl["rowptr"]))
+    mine = (own == me) | (own < 0)
+    # list A touches only this rank's subtree and the top tiles
+    assert np.all(mine[A["j"]]) and np.all(mine[A["i"]]) and np.all(mine[A["pp"]])
+    for ids in (A["t"], A["pt"]):
+        ids = ids[ids >= 0]
+        assert np.all(mine[row_of[ids]]) and np.all(mine[pl["cols"][ids]])
+    fa = A["kind"] == 0
+    assert np.all(own[A["j"][fa]] == me)            # it factors the subtree's columns ...
+    assert np.all(own[A["j"][A["kind"] >= 6]] < 0)  # ... and sums its contributions into top tiles / panels
+    # list B targets only top columns (factor and forward tasks), updated from top panels only
+    fb = (B["kind"] == 0) | (B["kind"] == 4)
+    assert np.all(own[B["j"][fb]] < 0)
+    for t in np.nonzero(fb)[0]:
+        assert np.all(own[B["pp"][B["pl0"][t]:B["pl0"][t + 1]]] < 0)
+    # together the two ranks' lists A and every rank's list B factor each tile once
+    fac = [(int(j), int(i)) for L in (A, B) for j, i in zip(L["j"][L["kind"] == 0], L["i"][L["kind"] == 0])]
+    want = [(int(pl["cols"][q]), int(row_of[q])) for q in range(pl["ntile"]) if mine[pl["cols"][q]]]
+    assert sorted(fac) == sorted(want)
+
+
 def test_random_sparse(plan_harness):
     rng = np.random.default_rng(3)
     for NP in (40, 120):
