@@ -128,7 +128,7 @@ def exported_symbols():
             "lba_set_farm_group", "lba_farm_plan", "lba_farm_exchange", "lba_farm_match", "lba_solver_info", "lba_solver_flops", "lba_device_bytes", "lba_setup_phases",
             "lba_kernel_modes", "lba_setup_host_profile", "lba_setup_tile_shapes", "lba_debug_pool_stress", "lba_debug_lie", "lba_partition_assign", "lba_kf_owner", "lba_split_info",
             "lba_track_vel_ransac", "lba_posegraph_optimize", "lba_posegraph_linearize", "lba_posegraph_step",
-            "lba_posegraph_plan_info", "lba_posegraph_profile"]
+            "lba_posegraph_plan_info", "lba_posegraph_profile", "lba_sim3_ransac", "lba_sim3_ransac_profile"]
 
 
 def setup_host_profile(win, **cfg_over):

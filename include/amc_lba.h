@@ -498,6 +498,73 @@ int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n_pairs, lba
  * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
 int lba_sim3_profile(lba_tracker* t, int32_t on, double* last_ms);
 
+/* ---- loop closing: the Sim3Solver RANSAC that runs before OptimizeSim3 (src/Sim3Solver.cc, driven by
+ * LoopClosing::DetectCommonRegionsFromBoW, src/LoopClosing.cc:527-539) for a batch of candidate pairs.  One call is
+ * the whole `while (!bNoMore && !bConverge) iterate(20, ...)` loop of every pair: the caller draws the
+ * mRansacMaxIts triples (amc_lba.sim3_ransac.draw_triples, :277-291) and filters the matches
+ * (amc_lba.sim3_ransac.sim3_ransac_rows, :85-147).
+ * Hypothesis (ComputeSim3, :343-459), in fp64 on the float-valued inputs widened: centroids of the triple's three
+ * columns and relative coordinates, M = Pr2 Pr1^T summed in column order, Horn's 4 x 4 symmetric N (:367-381), the
+ * eigenvector q = (w, vec) of its largest eigenvalue (a cyclic Jacobi of 6 fixed sweeps); |vec| < 1e-5 is DEGENERATE
+ * (quirk b); R12 the rotation of that unit quaternion (the reference's atan2 / SO3::exp route gives the same rotation
+ * whatever the sign of q); s12 = sum(Pr1 . R Pr2) / sum((R Pr2)^2), or 1 under fix_scale; t12 = O1 - s R O2;
+ * T21 = [(1/s) R^T | -(1/s) R^T t] (:452-458).
+ * Scoring (CheckInliers, Project, FromCameraToImage, :462-536): p11 = pi1(Tc1b[cam1] X1b), p22 = pi2(Tc2b[cam2] X2b)
+ * (the points' own projections, not keypoints), p21 = pi1(Tc1b[cam1] (s R X2b + t)), p12 = pi2(Tc2b[cam2] T21 X1b);
+ * a row is an inlier iff |p11 - p21|^2 < max_err1 AND |p12 - p22|^2 < max_err2, strictly.  Pinhole, no depth test; a
+ * non-finite error is an outlier; a point at z = 0 gives one and does not fault.
+ * Selection (iterate, :272-325) over the counts in hypothesis order, degenerate hypotheses skipped: `converged` is set
+ * at the FIRST hypothesis with inliers > min_inliers and that one is selected; otherwise the selected one is the LAST
+ * hypothesis whose count is >= every earlier one, from 0 (ties go to the later one, a count of 0 qualifies).  The
+ * chunking into iterate(20) calls changes nothing (the members carry over); bNoMore is !converged.  N < min_inliers
+ * (:257-261) is the caller's early exit: pass n_hyp = 0.
+ * Three quirks of the reference are kept:
+ *  (a) mvnMaxError1/2 are std::vector<size_t> (include/Sim3Solver.h:78-79), so 9.210 sigma2 (:129-130) is truncated
+ *      to an integer before the float comparison: 9 at level 0, 13 at level 1.  max_err1/2 are compared as given; the
+ *      caller passes floor(9.210 * (double)(float)sigma2).
+ *  (b) A degenerate hypothesis returns at :399-400 before assigning anything, and CheckInliers rescores the previous
+ *      hypothesis's transform: the previous count again, which can neither converge nor change the best values.  It is
+ *      skipped, which is exact wherever the reference is defined (on the very first hypothesis it reads uninitialised
+ *      members: skipped too), counted as 0 inliers and reported as LBA_S3R_DEGENERATE in hyp_flags.  Three exactly
+ *      coincident points give N = 0, whose first unit vector (1, 0, 0, 0) is the eigenvector Eigen's maxCoeff and
+ *      this solver both take: degenerate.
+ *  (c) A hypothesis whose transform is not finite (a NaN scale from non-finite coordinates) scores 0 inliers,
+ *      is reported as LBA_S3R_NONFINITE and can still be selected through 0 >= 0, as in the reference.
+ * A batch is two launches: one wave per hypothesis, then one per pair; a pair's result does not depend on the batch or
+ * on its position, and results are bitwise reproducible.
+ * LBA_E_ARG: null tracker or arrays, n_cam < 1, a pair's correspondence, hypothesis or camera range
+ * ([cam0, cam0 + 2 n_cam)) outside its array, cam1 / cam2 outside [0, n_cam), a triple with an index outside
+ * [0, n_corr) of its pair or with a repeated index, min_inliers < 0, a max_err that is NaN.  LBA_E_LIMIT: n_cam > 64
+ * (a pair's 2 n_cam camera records are kept in 16 KB of LDS), or a batch whose rows, hypotheses and inlier masks
+ * (n_hyp * ceil(n_corr / 64) words per pair) exceed 2 GB; a pair's n_corr and n_hyp have no limit of their own.
+ * A refused call writes nothing.  n_pairs == 0, n_corr == 0 and n_hyp == 0 for a pair (best_hyp = -1, every row
+ * inlier = 0, q / t / s untouched) are valid.  When the correspondence ranges of two pairs overlap, the shared rows
+ * carry the flags of the later pair.  hyp_S12 of a degenerate hypothesis is reported, not defined. */
+#define LBA_S3R_DEGENERATE 1   /* hyp_flags: |vec| < 1e-5, the hypothesis was skipped */
+#define LBA_S3R_NONFINITE  2   /* hyp_flags: q, t or s of the hypothesis is not finite */
+typedef struct lba_s3r_corr {
+    int32_t cam1, cam2;      /* mvncam1[i], mvncam2[i] (Sim3Solver.cc:93, :110-118) */
+    int32_t inlier;          /* out: the selected hypothesis's mvbInliersi[i]; 0 when none is selected */
+    int32_t pad;
+    double  X1b[3], X2b[3];  /* mvX3Db1[i], mvX3Db2[i] (float, widened; :136-140) */
+    double  max_err1, max_err2; /* mvnMaxError1/2[i] exactly as the reference holds them (quirk a) */
+} lba_s3r_corr;
+typedef struct lba_s3r_pair {
+    double  q[4], t[3], s;   /* out: mBestRotation (as (x, y, z, w), w >= 0), mBestTranslation, mBestScale of the
+                                selected hypothesis; untouched when best_hyp < 0 */
+    int32_t fix_scale, min_inliers;   /* mbFixScale, mRansacMinInliers */
+    int32_t corr0, n_corr, cam0;      /* cam0: its 2 n_cam lba_sim3_cam rows, KF1's then KF2's, as lba_sim3_optimize */
+    int32_t hyp0, n_hyp;              /* its triples in `samples`: pair-local row indices */
+    int32_t best_hyp, n_inliers, converged;   /* out: pair-local index or -1; its count or 0; bConverge */
+} lba_s3r_pair;
+int lba_sim3_ransac(lba_tracker* t, lba_s3r_pair* pairs, int32_t n_pairs, lba_s3r_corr* corr, int32_t n_corr,
+                    const int32_t* samples, int32_t n_hyp,   /* [3 * n_hyp] */
+                    const lba_sim3_cam* cams, int32_t n_cam_rows, int32_t n_cam,
+                    double* hyp_S12 /* [8 n_hyp]: q t s */, int32_t* hyp_inliers, int32_t* hyp_flags); /* each may be NULL */
+/* Measurement only: on != 0 makes lba_sim3_ransac bracket its two launches with two events on the tracker's stream;
+ * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
+int lba_sim3_ransac_profile(lba_tracker* t, int32_t on, double* last_ms);
+
 /* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
  * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
  * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one
