@@ -25,6 +25,28 @@ CAM_DTYPE = np.dtype([
     ("ext_free", "<i4"), ("pad", "<i4"), ("rbc_ini", "<f8", (4,)), ("rbc_info", "<f8", (9,)),
 ], align=True)
 
+# lba_triangulate (CreateNewMapPoints)
+TRI_CAM_DTYPE = np.dtype([
+    ("Tcw", "<f8", (12,)), ("Ow", "<f8", (3,)),
+    ("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"), ("invfx", "<f8"), ("invfy", "<f8"),
+], align=True)
+TRI_KF_DTYPE = np.dtype([
+    ("Rwb", "<f8", (9,)), ("twb", "<f8", (3,)), ("bf", "<f8"), ("b", "<f8"), ("cam0", "<i4"), ("pad", "<i4"),
+], align=True)
+TRI_ROW_DTYPE = np.dtype([
+    ("cam1", "<i4"), ("cam2", "<i4"), ("status", "<i4"), ("stereo_point", "<i4"),
+    ("z1", "<f8", (2,)), ("z2", "<f8", (2,)), ("k1", "<f8", (2,)), ("k2", "<f8", (2,)),
+    ("ur1", "<f8"), ("ur2", "<f8"), ("depth1", "<f8"), ("depth2", "<f8"),
+    ("sigma2_1", "<f8"), ("sigma2_2", "<f8"), ("scale1", "<f8"), ("scale2", "<f8"), ("X", "<f8", (3,)),
+], align=True)
+TRI_PAIR_DTYPE = np.dtype([
+    ("kf1", "<i4"), ("kf2", "<i4"), ("row0", "<i4"), ("n_rows", "<i4"), ("n_new", "<i4"), ("n_stereo", "<i4"),
+], align=True)
+assert TRI_CAM_DTYPE.itemsize == 168
+assert TRI_KF_DTYPE.itemsize == 120
+assert TRI_ROW_DTYPE.itemsize == 168
+assert TRI_PAIR_DTYPE.itemsize == 24
+
 assert KF_DTYPE.itemsize == 128
 assert OBS_DTYPE.itemsize == 64
 assert PRIOR_DTYPE.itemsize == 8

@@ -114,6 +114,12 @@ class Tracker:
             raise LbaError(rc, "lba_track_vel_ransac failed")
         return frames, obs, hyp
 
+    def triangulate(self, pairs, rows, kfs, cams, n_cam, params=None):
+        """LocalMapping::CreateNewMapPoints' triangulation for a batch of (keyframe, neighbour) pairs
+        (lba_triangulate; amc_lba.triangulate has the dtypes, the row construction and the generator)."""
+        from .triangulate import triangulate
+        return triangulate(self, pairs, rows, kfs, cams, n_cam, params)
+
 
 def mc_ransac(tracker, frames, obs, samples, cams, min_match=30, outlier=None, params=None):
     """Tracking::MCRansac for a batch of frames with the caller's triples: the hypotheses on the GPU, then the

@@ -565,6 +565,106 @@ int lba_sim3_ransac(lba_tracker* t, lba_s3r_pair* pairs, int32_t n_pairs, lba_s3
  * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
 int lba_sim3_ransac_profile(lba_tracker* t, int32_t on, double* last_ms);
 
+/* ---- local mapping: the triangulation of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:408-587, with
+ * GeometricTools::Triangulate, src/GeometricTools.cc:47-66, and MultiKeyFrame::UnprojectStereo, src/KeyFrame.cc:829-846)
+ * for a batch of (keyframe, neighbour) pairs, the step that makes the landmarks the next lba_set_problem receives.  One
+ * row is one match of SearchForTriangulation (which stays on the CPU, like Fuse: greedy matching on map state); the
+ * caller builds the rows (amc_lba.triangulate.tri_rows, :412-432, :498, :525, :565).  Per row, in fp64 on the
+ * float-valued inputs widened, in the reference's order; the row gets the FIRST status that applies:
+ *   rays      xn = ((u - cx) / fx, (v - cy) / fy, 1) of z1 / z2 with the row's camera (Pinhole::unprojectEig),
+ *             ray = Rcw^T xn, cosRays their normalised dot product (:434-439).
+ *   parallax  cosStereo1 = cosStereo2 = cosRays + 1; if side 1 is stereo (ur1 >= 0), cosStereo1 =
+ *             cos(2 atan2(b1 / 2, depth1)); ONLY if side 1 is not stereo and side 2 is, cosStereo2 likewise (:441-450,
+ *             quirk a); cosStereo = min of the two.  Evaluated as (d^2 - h^2) / (d^2 + h^2), h = b / 2, which is the same
+ *             function of a finite depth (d = h = 0 gives 1, as atan2(0, 0) does); there is no transcendental.
+ *   branch    triangulate when cosRays < cosStereo && cosRays > 0 && (stereo1 || stereo2 || cosRays < 0.9998); else
+ *             back-project from KF1 when stereo1 && cosStereo1 < cosStereo2; else from KF2 when stereo2 &&
+ *             cosStereo2 < cosStereo1; else LBA_TRI_PARALLAX (the final `else continue`, :461-481).
+ *   Triangulate  A's rows x1 T1[2] - T1[0], y1 T1[2] - T1[1], x2 T2[2] - T2[0], y2 T2[2] - T2[1] (GeometricTools.cc:
+ *             50-53); x3Dh the right singular vector of the smallest singular value (a one-sided Jacobi of 5 fixed
+ *             sweeps on the columns of A; of equal singular values the first column's); w == 0 or w not finite is
+ *             LBA_TRI_W_ZERO; X = x3Dh.head(3) / w, in which the vector's sign cancels.
+ *   UnprojectStereo  z = depth; z <= 0 (or NaN) is LBA_TRI_NO_DEPTH; x = (k.u - cx) z invfx, y = (k.v - cy) z invfy
+ *             with the RAW keypoint k and the LAST camera's cx, cy, invfx, invfy of that keyframe (cams[cam0 + n_cam -
+ *             1]); X = Rwb (x, y, z) + twb: the BODY pose, not the camera's (quirk b).  stereo_point is set.
+ *   gates     z1 = Tcw1[2] . (X, 1) <= 0: LBA_TRI_BEHIND1; z2 likewise: LBA_TRI_BEHIND2 (:489-495).  Reprojection in KF1
+ *             then KF2 (:497-549): a mono side (ur < 0) drops e^2 > 5.991 sigma2 with u = fx x / z + cx; a stereo side
+ *             drops ex^2 + ey^2 + er^2 > 7.8 sigma2 with invz = 1 / z, u = fx x invz + cx, u_r = u - bf invz, against z
+ *             (the undistorted keypoint) and ur: LBA_TRI_REPROJ1 / LBA_TRI_REPROJ2.  dist = |X - Ow| of either camera;
+ *             dist1 == 0 || dist2 == 0: LBA_TRI_DIST_ZERO (:558); far_points && (dist1 >= th_far || dist2 >= th_far):
+ *             LBA_TRI_FAR (:561); ratioDist = dist2 / dist1, ratioOctave = scale1 / scale2, ratioDist ratio_factor <
+ *             ratioOctave || ratioDist > ratioOctave ratio_factor: LBA_TRI_SCALE (:564-568).  Otherwise LBA_TRI_OK and X.
+ * Quirks of the reference that are kept:
+ *  (a) the `else if` of :448: with both sides stereo only cosStereo1 is computed, cosStereo2 stays cosRays + 1, so the
+ *      back-projection can only come from KF1.
+ *  (b) UnprojectStereo reads mvKeys (raw), the last camera's intrinsics and mRwb / mTwb, whatever camera the keypoint
+ *      is in; tri_rows sets ur only for keypoints of the last camera, as :419-432 do.
+ *  (c) every comparison is the reference's, so a NaN falls where it falls there: NaN <= 0 and NaN > gate are false, and
+ *      a row with a NaN keypoint can come back LBA_TRI_OK with a NaN X, as the reference would create the point.
+ *      Nothing loops on data.
+ *  (d) LBA_TRI_DIST_ZERO cannot be reached with an Ow that is the camera's centre (z > 0 comes first); it stays because
+ *      the device compares what it is given.
+ * The reference computes all of this in float; the status of a row within float rounding of a gate can differ
+ * (DESIGN.md §7 item 10 measures how often).
+ * prm == NULL means ratio_factor = 1.5 * 1.2 and far_points = 0; the reference's is (double)(1.5f * mfScaleFactor)
+ * (amc_lba.triangulate.ratio_factor).  n_new / n_stereo of a pair are `total` and `countStereo` (:572-574): its rows
+ * with LBA_TRI_OK, and those of them with stereo_point.
+ * A batch is one upload, one launch (one thread per row, one workgroup per 64 rows of a pair) and one download; a
+ * row's result does not depend on the batch or on its position, and results are bitwise reproducible.
+ * LBA_E_ARG: null tracker or arrays, a negative count, n_cam < 1, a pair's kf1 / kf2 outside [0, n_kf) or its rows
+ * outside [0, n_rows), a keyframe's cameras [cam0, cam0 + n_cam) outside [0, n_cam_rows), cam1 / cam2 of a row of a
+ * pair outside [0, n_cam), a ratio_factor that is not finite or not positive.  LBA_E_LIMIT: n_cam > 64 (a pair's
+ * 2 n_cam camera records are kept in LDS), or an arena above 2 GB.  A refused call writes nothing.  n_pairs == 0 and a
+ * pair with n_rows == 0 (n_new = n_stereo = 0) are valid.  Rows shared by two pairs carry the later pair's result. */
+#define LBA_TRI_OK        0
+#define LBA_TRI_PARALLAX  1    /* not enough parallax and no usable stereo depth */
+#define LBA_TRI_W_ZERO    2    /* Triangulate returned false */
+#define LBA_TRI_NO_DEPTH  3    /* UnprojectStereo found z <= 0 */
+#define LBA_TRI_BEHIND1   4
+#define LBA_TRI_BEHIND2   5
+#define LBA_TRI_REPROJ1   6
+#define LBA_TRI_REPROJ2   7
+#define LBA_TRI_DIST_ZERO 8
+#define LBA_TRI_FAR       9
+#define LBA_TRI_SCALE     10
+typedef struct lba_tri_cam {   /* one per (keyframe, camera) */
+    double Tcw[12];            /* GetCameraPose(c).matrix3x4(), row-major, float widened (:360-361, :393-394) */
+    double Ow[3];              /* GetCameraCenter(c) as the map holds it (:365, :398) */
+    double fx, fy, cx, cy, invfx, invfy;   /* mvfx.. / minvfx.. of that camera, as held */
+} lba_tri_cam;
+typedef struct lba_tri_kf {
+    double Rwb[9], twb[3];     /* mRwb (row-major), mTwb.translation(): what UnprojectStereo uses (KeyFrame.cc:841) */
+    double bf, b;              /* mbf, mb */
+    int32_t cam0, pad;         /* its n_cam rows of `cams` */
+} lba_tri_kf;
+typedef struct lba_tri_row {
+    int32_t cam1, cam2;        /* mmpKeyToCam[idx1], [idx2] */
+    int32_t status;            /* out: LBA_TRI_* */
+    int32_t stereo_point;      /* out: bPointStereo */
+    double  z1[2], z2[2];      /* mvKeysUn[idx].pt */
+    double  k1[2], k2[2];      /* mvKeys[idx].pt: UnprojectStereo reads the raw keypoint (KeyFrame.cc:834-835) */
+    double  ur1, ur2;          /* kp_ur: mvuRight[...] for the last camera, -1 otherwise (:419-432); bStereo = ur >= 0 */
+    double  depth1, depth2;    /* mvDepth[mmpGlobalToLocalID[idx]] (read only when that side is stereo) */
+    double  sigma2_1, sigma2_2;/* mvLevelSigma2[octave] */
+    double  scale1, scale2;    /* mvScaleFactors[octave] */
+    double  X[3];              /* out: x3D when status == LBA_TRI_OK, otherwise untouched */
+} lba_tri_row;
+typedef struct lba_tri_pair {
+    int32_t kf1, kf2;          /* indices into `kfs`: mpCurrentKeyFrame, vpNeighKFs[i] */
+    int32_t row0, n_rows;
+    int32_t n_new, n_stereo;   /* out: `total` and `countStereo` of this pair */
+} lba_tri_pair;
+typedef struct lba_tri_params {
+    double  ratio_factor, th_far;   /* 1.5f * mfScaleFactor; mThFarPoints */
+    int32_t far_points, pad;        /* mbFarPoints */
+} lba_tri_params;
+int lba_triangulate(lba_tracker* t, lba_tri_pair* pairs, int32_t n_pairs, lba_tri_row* rows, int32_t n_rows,
+                    const lba_tri_kf* kfs, int32_t n_kf, const lba_tri_cam* cams, int32_t n_cam_rows, int32_t n_cam,
+                    const lba_tri_params* prm /* may be NULL */);
+/* Measurement only: on != 0 makes lba_triangulate bracket its launch with two events on the tracker's stream;
+ * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
+int lba_triangulate_profile(lba_tracker* t, int32_t on, double* last_ms);
+
 /* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
  * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
  * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one

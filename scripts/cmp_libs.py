@@ -2,8 +2,8 @@
 its own child process, selected by AMC_LBA_LIB ("main": the tree's library):
     python scripts/cmp_libs.py <lib A> <lib B> [config]    LM runs of Problem.optimize on a window config
     python scripts/cmp_libs.py <lib A> <lib B> tracker     every entry point of the tracker handle (lba_track,
-        lba_track_vel_ransac, lba_sim3_optimize, lba_posegraph_optimize), each case with early_stop 0 and 1, on the
-        smallest shapes that reach every branch of their LM loops; every output array is hashed."""
+        lba_track_vel_ransac, lba_sim3_optimize, lba_sim3_ransac, lba_posegraph_optimize), each case with early_stop 0
+        and 1, on the smallest shapes that reach every branch of their LM loops; every output array is hashed."""
 import hashlib
 import json
 import os
@@ -58,6 +58,11 @@ def child_tracker():
                 p, c, cams, _ = make_sim3_pairs(n_pairs=3, n_corr=n_corr, n_cam=4, seed=71, fix_scale=fix_scale)
                 p, c = t.sim3_optimize(p, c, cams, 4)
                 out[f"sim3 n_corr={n_corr} fix_scale={int(fix_scale)} es={es}"] = _h(p, c)
+        for n_corr in (20, 129):                             # one / three mask words per hypothesis
+            from amc_lba.sim3_ransac import make_sim3_ransac_pairs
+            p, c, s, cams, _ = make_sim3_ransac_pairs(n_pairs=2, n_corr=n_corr, n_hyp=40, seed=61, min_inliers=6)
+            p, c, hyp = t.sim3_ransac(p, c, s, cams, 4)
+            out[f"sim3_ransac n_corr={n_corr} es={es}"] = _h(p, c, *[hyp[k] for k in sorted(hyp)])
         for name in ("loop150", "hub"):
             for lam in (1e-16, 0.0):                         # the user's lambda / computeLambdaInit
                 v, e, fix = pc.case(name)
