@@ -47,6 +47,28 @@ assert TRI_KF_DTYPE.itemsize == 120
 assert TRI_ROW_DTYPE.itemsize == 168
 assert TRI_PAIR_DTYPE.itemsize == 24
 
+# lba_match_project (ORBmatcher::SearchByProjection)
+MATCH_CAM_DTYPE = np.dtype([
+    ("min_x", "<f4"), ("min_y", "<f4"), ("grid_w_inv", "<f4"), ("grid_h_inv", "<f4"), ("rounds", "<i4"),
+], align=True)
+MATCH_FEAT_DTYPE = np.dtype([
+    ("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("u_right", "<f4"), ("octave", "<i4"), ("cam", "<i4"),
+    ("taken", "<i4"), ("job", "<i4"), ("desc", "<u4", (8,)),
+], align=True)
+MATCH_JOB_DTYPE = np.dtype([
+    ("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("ur", "<f4"), ("angle", "<f4"), ("cam", "<i4"),
+    ("min_level", "<i4"), ("max_level", "<i4"), ("point", "<i4"), ("blocks", "<i4"), ("desc", "<u4", (8,)),
+    ("feat", "<i4"), ("status", "<i4"), ("best_dist", "<i4"), ("best_dist2", "<i4"), ("pad", "<i4", (2,)),
+], align=True)
+MATCH_SEARCH_DTYPE = np.dtype([
+    ("cam0", "<i4"), ("n_cam", "<i4"), ("feat0", "<i4"), ("n_feat", "<i4"), ("job0", "<i4"), ("n_jobs", "<i4"),
+    ("cell0", "<i4"), ("cf0", "<i4"), ("n_matches", "<i4"), ("n_matches_mono", "<i4"),
+], align=True)
+assert MATCH_CAM_DTYPE.itemsize == 20
+assert MATCH_FEAT_DTYPE.itemsize == 64
+assert MATCH_JOB_DTYPE.itemsize == 96
+assert MATCH_SEARCH_DTYPE.itemsize == 40
+
 assert KF_DTYPE.itemsize == 128
 assert OBS_DTYPE.itemsize == 64
 assert PRIOR_DTYPE.itemsize == 8

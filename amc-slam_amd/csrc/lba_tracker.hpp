@@ -1,6 +1,6 @@
 // lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip),
 // lba_track_vel_ransac (lba_track_vel.hip), lba_sim3_ransac (lba_sim3_ransac.hip), lba_sim3_optimize (lba_sim3.hip),
-// lba_posegraph_* (lba_posegraph.hip) and lba_triangulate (lba_triangulate.hip),
+// lba_posegraph_* (lba_posegraph.hip), lba_triangulate (lba_triangulate.hip) and lba_match_project (lba_match.hip),
 // and what they have in common on the host: the error path, the per-call arena and the camera records.
 // One stream, device buffers that grow and are reused across calls.  Calls on a tracker are serial.
 #pragma once
@@ -28,7 +28,7 @@ struct lba_tracker {
     // lba_track_vel_ransac / lba_sim3_optimize / lba_posegraph_*: one arena per call (inputs, outputs, work)
     char* d_arena = nullptr;
     size_t arena_cap = 0;                // in bytes
-    char* h_sim3 = nullptr;              // lba_sim3_optimize / lba_sim3_ransac / lba_triangulate: the pinned host image of the arena
+    char* h_sim3 = nullptr;              // lba_sim3_optimize / lba_sim3_ransac / lba_triangulate / lba_match_project: the pinned host image of the arena
     size_t sim3_pin_cap = 0;
     bool sim3_timed = false;             // lba_sim3_profile: bracket the launch with events
     hipEvent_t sim3_ev[2] = {nullptr, nullptr};
@@ -37,6 +37,9 @@ struct lba_tracker {
     double s3r_ms = -1.0;
     bool tri_timed = false;              // lba_triangulate_profile: the same bracket (and events) for its launch
     double tri_ms = -1.0;
+    bool match_timed = false;            // lba_match_profile: events around lba_match_project's two launches
+    hipEvent_t match_ev[3] = {nullptr, nullptr, nullptr};
+    double match_ms[2] = {-1.0, -1.0};   // k_match_gather, k_match_resolve
     double pg_ms[3] = {-1.0, -1.0, -1.0};   // lba_posegraph_profile: planning, upload, device of the last optimize
     std::string err;
     // every buffer and event is freed here and nowhere else (lba_tracker_destroy: device, synchronise, stream, delete)
@@ -46,6 +49,8 @@ struct lba_tracker {
             if (b) (void)hipFree(b);
         if (h_sim3) (void)hipHostFree(h_sim3);
         for (hipEvent_t e : sim3_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : match_ev)
             if (e) (void)hipEventDestroy(e);
     }
 };

@@ -665,6 +665,127 @@ int lba_triangulate(lba_tracker* t, lba_tri_pair* pairs, int32_t n_pairs, lba_tr
  * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
 int lba_triangulate_profile(lba_tracker* t, int32_t on, double* last_ms);
 
+/* ---- tracking: ORBmatcher's two projection searches for a batch of frames: SearchByProjection(MultiFrame&,
+ * const vector<MapPoint*>&, th, ...) (src/ORBmatcher.cc:43-217, Tracking::SearchLocalPoints) is LBA_MATCH_RATIO, and
+ * SearchByProjection(MultiFrame& Current, const MultiFrame& Last, th, bMono) (:1439-1568, TrackWithMotionModel) is
+ * LBA_MATCH_BEST.  A *search* is one frame with its ordered job list; a *job* is one (map point, camera) pair the
+ * reference's loops reach, in their order (point-major, cameras inner).  The caller projects (isInFrustum's fields, or
+ * uv / invzc / the octave: amc_lba.match.jobs_local_points / jobs_last_frame) and passes the results as floats:
+ * reproducing Eigen's float SE3f * Vector3f bit for bit is not a goal of this entry point.
+ *
+ * Per job, MultiFrame::GetFeaturesInArea (src/Frame.cc:608-673) on the caller's grid (a CSR of the 64 x 48 cells per
+ * camera, cells in [ix][iy] order, a cell's features in AssignFeaturesToGrid's insertion order): the cell rectangle
+ *   max(0, (int)floor((x - min_x - radius) * grid_w_inv)) .. min(63, (int)ceil((x - min_x + radius) * grid_w_inv))
+ * and its y sibling, the level test, fabs(kx - x) < radius && fabs(ky - y) < radius; then, per candidate in
+ * (ix, iy, position in cell) order: skip a taken feature, the stereo gate (u_right > 0 and fabs(ur - u_right) >
+ * radius skips), the 256-bit Hamming distance, best (LBA_MATCH_BEST) or best and second best with their levels
+ * (LBA_MATCH_RATIO), `dist < bestDist` strict.  Accepted (LBA_MATCH_OK): bestDist <= th_high, and in LBA_MATCH_RATIO
+ * not (bestLevel == bestLevel2 && bestDist > nn_ratio * bestDist2).  An accepted job writes its point to its best
+ * feature, and if `blocks` (the point's Observations() > 0) that feature is taken for every later job.
+ * Every floating-point expression that decides something is evaluated in FLOAT, in the reference's order, without
+ * contraction (a stated departure from the tracker's fp64-on-widened-inputs convention): each is
+ * one to three IEEE single operations, so the decisions are the reference's own bits and all outputs are exact.
+ * With check_orientation (LBA_MATCH_BEST only) the rotation histogram of :1526-1567 with ComputeThreeMaxima follows:
+ * rot = job.angle - feat.angle, +360 if negative, bin = round(rot * (1.0f / 30)), 30 -> 0; the jobs of every bin that is
+ * not one of the (up to) three maxima become LBA_MATCH_ROT, their features' `job` -1, and n_matches loses one each.
+ * Quirks of the reference that are kept:
+ *  (a) bCheckLevels = (min_level > 0) || (max_level >= 0): a min_level of 0 or -1 with max_level < 0 checks nothing;
+ *      octave < min_level is applied even where max_level < 0.
+ *  (b) the last-frame function truncates: `int uRight = mvuRight[..]` before `uRight > 0` and before the subtraction
+ *      (:1500-1503); the local-points function compares the float (:95-98).  params.ur_truncate selects.
+ *  (c) the window's high side uses ceil, so it reaches one cell further than floor; PosInGrid rounds.  The caller's CSR
+ *      is the reference's grid, so both stay.
+ *  (d) ties go to the first candidate in (ix, iy, position in cell) order; a single candidate is accepted in
+ *      LBA_MATCH_RATIO (bestLevel2 stays -1); a candidate at distance 256 is never chosen (256 < 256 is false).
+ *  (e) x, y or radius not finite, or a floor / ceil value outside int's range, is undefined behaviour there
+ *      ((int)floor(NaN)); here such a job has no candidates (LBA_MATCH_NO_CAND).  The values are clamped in float
+ *      before the conversion; for every finite in-range value the result is the reference's.
+ *  (f) the rotation pass clears mvpMapPoints[feature] for EVERY entry of a losing bin: a feature that a non-blocking
+ *      job of a losing bin won and a later job of a surviving bin overwrote ends with `job` -1 although the later job
+ *      stays LBA_MATCH_OK.  n_matches_mono is not reduced by the rotation pass (the reference's nmatches_mono is not).
+ * n_matches counts accepted jobs including overwrites; n_matches_mono those with cam < n_cam - 1.
+ *
+ * Device: k_match_gather, one 64-lane wave per job, writes each job's candidates (gates applied, `taken` not) in
+ * order; k_match_resolve, one workgroup per (search, camera), reproduces the sequential loop exactly in rounds (a job is
+ * final once no earlier pending job of its camera shares an untaken candidate with it); cam.rounds reports the count,
+ * at most the camera's job count, 0 for a camera without jobs.  One upload, two launches, one download; nothing waits
+ * on another workgroup.  The rotation pass and the counts run on the host after the download.
+ * LBA_E_ARG: null tracker or arrays; a negative count; a search's camera, feature, job, cell_start or cell_feat range
+ * outside its array, or its cameras, features or jobs beginning before the end of the search before (the searches lie
+ * one behind the other); n_cam < 1; cell_start not starting at 0 or decreasing, or past n_cell_feat; a cell_feat entry
+ * outside [0, n_feat) or naming a feature of another camera than the cell's; a feature's cam outside [0, n_cam) or its
+ * octave outside [0, 255]; a job's cam outside [0, n_cam) or min_level > max_level where max_level >= 0; mode not
+ * one of the two; th_high outside [0, 255]; nn_ratio NaN; stereo_cam outside [-1, n_cam) of any search;
+ * check_orientation with LBA_MATCH_RATIO.  LBA_E_LIMIT: more than LBA_MATCH_MAX_FEAT features in one camera (the
+ * resolve kernel keeps a word and a bit per feature in LDS), or an arena above 2 GB.  A refused call writes nothing
+ * and sets the text lba_tracker_last_error returns.  n_searches == 0, a search without jobs or without features
+ * are valid. */
+#define LBA_MATCH_RATIO 0
+#define LBA_MATCH_BEST  1
+#define LBA_MATCH_OK       0
+#define LBA_MATCH_NO_CAND  1   /* vIndices empty, or every candidate skipped (taken / stereo gate) */
+#define LBA_MATCH_TOO_FAR  2   /* bestDist > th_high */
+#define LBA_MATCH_RATIO_FAIL 3 /* LBA_MATCH_RATIO: equal levels and bestDist > nn_ratio * bestDist2 */
+#define LBA_MATCH_ROT      4   /* accepted, then removed by the rotation check */
+#define LBA_MATCH_MAX_FEAT 8192
+#define LBA_MATCH_GRID_COLS 64
+#define LBA_MATCH_GRID_ROWS 48
+typedef struct lba_match_cam {     /* one per (search, camera) */
+    float   min_x, min_y;          /* mvMinX[c], mvMinY[c] */
+    float   grid_w_inv, grid_h_inv;/* mvGridElementWidthInv[c], mvGridElementHeightInv[c] */
+    int32_t rounds;                /* out: rounds k_match_resolve needed for this camera's jobs */
+} lba_match_cam;
+typedef struct lba_match_feat {    /* 64 bytes */
+    float    x, y;                 /* mvKeysUn[idx].pt */
+    float    angle;                /* mvKeysUn[idx].angle */
+    float    u_right;              /* mvuRight[mmpGlobalToLocalID[idx]]; <= 0: none */
+    int32_t  octave;               /* mvKeysUn[idx].octave, 0 .. 255 */
+    int32_t  cam;                  /* mmpKeyToCam[idx] */
+    int32_t  taken;                /* in: mvpMapPoints[idx] holds a point with Observations() > 0 on entry */
+    int32_t  job;                  /* out: search-local index of the job whose point it holds at the end, or -1 */
+    uint32_t desc[8];
+} lba_match_feat;
+typedef struct lba_match_job {     /* 96 bytes */
+    float    x, y;                 /* mvTrackProjX / Y[c], or uv */
+    float    radius;               /* r * mvScaleFactors[level] (the float product), or th * mvScaleFactors[octave] */
+    float    ur;                   /* mvTrackProjXR[c], or uv(0) - mbf * invzc */
+    float    angle;                /* LBA_MATCH_BEST with check_orientation: LastFrame.mvKeysUn[i].angle */
+    int32_t  cam;
+    int32_t  min_level, max_level;
+    int32_t  point;                /* opaque, echoed */
+    int32_t  blocks;               /* the point's Observations() > 0 */
+    uint32_t desc[8];              /* pMP->GetDescriptor() */
+    int32_t  feat;                 /* out: search-local feature won (kept under LBA_MATCH_ROT), or -1 */
+    int32_t  status;               /* out: LBA_MATCH_* */
+    int32_t  best_dist, best_dist2;/* out: bestDist, bestDist2 (256: none; best_dist2 is 256 in LBA_MATCH_BEST) */
+    int32_t  pad[2];
+} lba_match_job;
+typedef struct lba_match_search {
+    int32_t cam0, n_cam;           /* its rows of `cams` */
+    int32_t feat0, n_feat;         /* its rows of `feats`; cell_feat and the outputs number them from 0 */
+    int32_t job0, n_jobs;          /* its rows of `jobs`, in the reference's loop order */
+    int32_t cell0;                 /* its n_cam * 64 * 48 + 1 entries of `cell_start` (offsets from cf0, the first 0) */
+    int32_t cf0;                   /* its entries of `cell_feat` */
+    int32_t n_matches, n_matches_mono;   /* out */
+} lba_match_search;
+typedef struct lba_match_params {
+    int32_t mode;                  /* LBA_MATCH_RATIO / LBA_MATCH_BEST */
+    int32_t th_high;               /* TH_HIGH (100) */
+    float   nn_ratio;              /* mfNNratio */
+    int32_t stereo_cam;            /* camera whose features pass the u_right gate (the reference: n_cam - 1); -1 none */
+    int32_t ur_truncate;           /* quirk (b) */
+    int32_t check_orientation;     /* mbCheckOrientation; LBA_MATCH_BEST only */
+} lba_match_params;
+int lba_match_project(lba_tracker* t, lba_match_search* searches, int32_t n_searches, lba_match_cam* cams,
+                      int32_t n_cams, const int32_t* cell_start, int32_t n_cell_start, const int32_t* cell_feat,
+                      int32_t n_cell_feat, lba_match_feat* feats, int32_t n_feats, lba_match_job* jobs, int32_t n_jobs,
+                      const lba_match_params* prm);
+/* Measurement only: on != 0 makes lba_match_project bracket its two launches with events on the tracker's stream;
+ * last_ms (may be NULL) receives {k_match_gather, k_match_resolve} of the last such call in milliseconds, or -1. */
+int lba_match_profile(lba_tracker* t, int32_t on, double* last_ms /* [2] */);
+/* The text of the last refusal or failure of a call on this tracker ("" before the first). */
+const char* lba_tracker_last_error(const lba_tracker* t);
+
 /* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
  * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
  * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one
