@@ -150,6 +150,9 @@ def test_gpu_extrinsic_optimize_matches_oracle(name):
     assert n == n_o and st.trials == st_o.trials and st.result == st_o.result
     assert abs(st.chi2_final - st_o.chi2_final) <= 1e-7 * st_o.chi2_final
     assert _rel(kf["t"], kf_o["t"]) <= 1e-6 and _rel(lm, lm_o) <= 1e-6
+    kq, kqo = kf["q"] * np.sign(kf["q"][:, 3:4]), kf_o["q"] * np.sign(kf_o["q"][:, 3:4])
+    assert np.abs(kq - kqo).max() <= 1e-7
+    assert _rel(kf["vel"], kf_o["vel"]) <= 1e-5
     q, qo = cam["q"] * np.sign(cam["q"][:, 3:4]), cam_o["q"] * np.sign(cam_o["q"][:, 3:4])
     assert np.abs(q - qo).max() <= 1e-7
     assert _rel(cam["t"], cam_o["t"]) <= 1e-6

@@ -170,15 +170,18 @@ def active_vertices(win):
     return np.nonzero(act & ~fixed)[0], np.unique(o["lm"])
 
 
-def unshuffle_system(H, b, Hll, win, win_s, perms):
-    """(H_pp, b, H_ll) of the shuffled window win_s in the vertex order of the original window `win`."""
+def unshuffle_system(H, b, Hll, win, win_s, perms, n_tail=0):
+    """(H_pp, b, H_ll) of the shuffled window win_s in the vertex order of the original window `win`.  The last
+    n_tail pose rows (the free extrinsics' 6 each, in camera order: `shuffled` leaves the cameras alone) stay where
+    they are, behind the keyframe blocks."""
     kf0, lm0 = active_vertices(win)
     kfs, lms = active_vertices(win_s)
     pos_k = {int(perms["kf"][k]): i for i, k in enumerate(kfs)}     # original keyframe -> block in the shuffle
     pos_l = {int(perms["lm"][l]): i for i, l in enumerate(lms)}
-    ip = np.concatenate([12 * pos_k[int(k)] + np.arange(12) for k in kf0]) if len(kf0) else np.zeros(0, np.int64)
+    ip = np.concatenate([12 * pos_k[int(k)] + np.arange(12) for k in kf0] + [12 * len(kfs) + np.arange(n_tail)])
+    ip = ip.astype(np.int64)
     il = np.concatenate([3 * pos_l[int(l)] + np.arange(3) for l in lm0]) if len(lm0) else np.zeros(0, np.int64)
-    np_ = 12 * len(kfs)
+    np_ = 12 * len(kfs) + n_tail
     assert H.shape == (np_, np_) and b.shape == (np_ + 3 * len(lms),)
     Hll0 = np.empty_like(Hll)
     Hll0[perms["lm"]] = Hll
