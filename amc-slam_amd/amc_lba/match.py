@@ -15,7 +15,7 @@ import numpy as np
 
 from . import LbaError
 from .abi import MATCH_CAM_DTYPE, MATCH_FEAT_DTYPE, MATCH_JOB_DTYPE, MATCH_SEARCH_DTYPE, ptr
-from .track import Tracker, _bind as _bind_track
+from .track import Tracker, _bind as _bind_track, kernel_ms
 
 MATCH_RATIO, MATCH_BEST = 0, 1
 MATCH_OK, MATCH_NO_CAND, MATCH_TOO_FAR, MATCH_RATIO_FAIL, MATCH_ROT = range(5)
@@ -49,7 +49,6 @@ def _bind():
         vp, i32 = ctypes.c_void_p, ctypes.c_int32
         L.lba_match_project.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32,
                                         ctypes.POINTER(LbaMatchParams)]
-        L.lba_match_profile.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_double)]
         L.lba_tracker_last_error.argtypes = [vp]
         L.lba_tracker_last_error.restype = ctypes.c_char_p
         L._match_bound = True
@@ -79,13 +78,8 @@ def match_project(tracker, searches, cams, cell_start, cell_feat, feats, jobs, p
 
 
 def match_kernel_ms(tracker, on=True):
-    """Measurement: switch the event brackets of lba_match_project's launches on or off; returns (k_match_gather,
-    k_match_resolve) of the last bracketed call in milliseconds (-1 before the first)."""
-    ms = (ctypes.c_double * 2)(-1.0, -1.0)
-    rc = _bind().lba_match_profile(tracker.h, int(bool(on)), ms)
-    if rc != 0:
-        raise LbaError(rc, "lba_match_profile failed")
-    return ms[0], ms[1]
+    """track.kernel_ms for lba_match_project's two launches: (k_match_gather, k_match_resolve)"""
+    return kernel_ms(tracker, "lba_match_profile", on, 2)
 
 
 Tracker.match_project = match_project

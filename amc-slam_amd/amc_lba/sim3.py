@@ -10,7 +10,7 @@ import numpy as np
 
 from . import LbaError
 from .abi import ptr
-from .track import Tracker, _bind as _bind_track
+from .track import Tracker, _bind as _bind_track, kernel_ms
 
 SIM3_CAM_DTYPE = np.dtype([
     ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"),
@@ -36,7 +36,6 @@ def _bind():
     if not getattr(L, "_sim3_bound", False):
         vp = ctypes.c_void_p
         L.lba_sim3_optimize.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32]
-        L.lba_sim3_profile.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
         L._sim3_bound = True
     return L
 
@@ -56,13 +55,8 @@ def sim3_optimize(tracker, pairs, corr, cams, n_cam):
 
 
 def sim3_kernel_ms(tracker, on=True):
-    """Measurement: switch the event bracket of lba_sim3_optimize's launch on or off; returns the kernel time of the
-    last bracketed call in milliseconds (-1 before the first)."""
-    ms = ctypes.c_double(-1.0)
-    rc = _bind().lba_sim3_profile(tracker.h, int(bool(on)), ctypes.byref(ms))
-    if rc != 0:
-        raise LbaError(rc, "lba_sim3_profile failed")
-    return ms.value
+    """track.kernel_ms for lba_sim3_optimize's launch"""
+    return kernel_ms(tracker, "lba_sim3_profile", on)
 
 
 Tracker.sim3_optimize = sim3_optimize

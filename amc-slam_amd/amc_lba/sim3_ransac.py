@@ -14,7 +14,7 @@ import numpy as np
 from . import LbaError
 from .abi import ptr
 from .sim3 import SIM3_CAM_DTYPE, SIM3_PAIR_DTYPE, _bind as _bind_sim3, make_sim3_pairs
-from .track import Tracker
+from .track import Tracker, kernel_ms
 
 S3R_CORR_DTYPE = np.dtype([
     ("cam1", "<i4"), ("cam2", "<i4"), ("inlier", "<i4"), ("pad", "<i4"),
@@ -40,7 +40,6 @@ def _bind():
         vp = ctypes.c_void_p
         L.lba_sim3_ransac.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32,
                                       ctypes.c_int32, vp, vp, vp]
-        L.lba_sim3_ransac_profile.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
         L._s3r_bound = True
     return L
 
@@ -65,13 +64,8 @@ def sim3_ransac(tracker, pairs, corr, samples, cams, n_cam, per_hyp=True):
 
 
 def sim3_ransac_kernel_ms(tracker, on=True):
-    """Measurement: switch the event bracket of lba_sim3_ransac's two launches on or off; returns the kernel time of
-    the last bracketed call in milliseconds (-1 before the first)."""
-    ms = ctypes.c_double(-1.0)
-    rc = _bind().lba_sim3_ransac_profile(tracker.h, int(bool(on)), ctypes.byref(ms))
-    if rc != 0:
-        raise LbaError(rc, "lba_sim3_ransac_profile failed")
-    return ms.value
+    """track.kernel_ms for lba_sim3_ransac's two launches together"""
+    return kernel_ms(tracker, "lba_sim3_ransac_profile", on)
 
 
 Tracker.sim3_ransac = sim3_ransac

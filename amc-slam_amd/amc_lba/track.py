@@ -60,6 +60,18 @@ def _bind():
     return L
 
 
+def kernel_ms(tracker, profile, on, n=1):
+    """Measurement: switch the event bracket of one entry point (`profile`: its lba_*_profile function) on or off;
+    returns the `n` kernel times of its last bracketed call in milliseconds (-1 before the first), a float for n = 1."""
+    fn = getattr(_bind(), profile)
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
+    ms = (ctypes.c_double * n)(*[-1.0] * n)
+    rc = fn(tracker.h, int(bool(on)), ms)
+    if rc != 0:
+        raise LbaError(rc, profile + " failed")
+    return ms[0] if n == 1 else tuple(ms)
+
+
 def track_config(**over):
     """The reference's tracking optimiser: Huber deltas as LocalGPBA, no user lambda
     (computeLambdaInit, src/Optimizer.cc:379-381), g2o stop rules."""

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import LbaError
 from .abi import TRI_CAM_DTYPE, TRI_KF_DTYPE, TRI_PAIR_DTYPE, TRI_ROW_DTYPE, ptr
-from .track import Tracker, _bind as _bind_track
+from .track import Tracker, _bind as _bind_track, kernel_ms
 
 (TRI_OK, TRI_PARALLAX, TRI_W_ZERO, TRI_NO_DEPTH, TRI_BEHIND1, TRI_BEHIND2, TRI_REPROJ1, TRI_REPROJ2, TRI_DIST_ZERO,
  TRI_FAR, TRI_SCALE) = range(11)
@@ -44,7 +44,6 @@ def _bind():
         vp = ctypes.c_void_p
         L.lba_triangulate.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, ctypes.c_int32,
                                       ctypes.c_int32, ctypes.POINTER(LbaTriParams)]
-        L.lba_triangulate_profile.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
         L._tri_bound = True
     return L
 
@@ -65,13 +64,8 @@ def triangulate(tracker, pairs, rows, kfs, cams, n_cam, params=None):
 
 
 def triangulate_kernel_ms(tracker, on=True):
-    """Measurement: switch the event bracket of lba_triangulate's launch on or off; returns the kernel time of the
-    last bracketed call in milliseconds (-1 before the first)."""
-    ms = ctypes.c_double(-1.0)
-    rc = _bind().lba_triangulate_profile(tracker.h, int(bool(on)), ctypes.byref(ms))
-    if rc != 0:
-        raise LbaError(rc, "lba_triangulate_profile failed")
-    return ms.value
+    """track.kernel_ms for lba_triangulate's launch"""
+    return kernel_ms(tracker, "lba_triangulate_profile", on)
 
 
 Tracker.triangulate_kernel_ms = triangulate_kernel_ms

@@ -195,16 +195,8 @@ __global__ __launch_bounds__(MR_WG) void k_match_resolve(MatchArgs A) {
 
 }  // namespace
 
-extern "C" const char* lba_tracker_last_error(const lba_tracker* t) { return t ? t->err.c_str() : "null tracker"; }
-
 extern "C" int lba_match_profile(lba_tracker* t, int32_t on, double* last_ms) {
-    if (!t) return LBA_E_ARG;
-    t->match_timed = on != 0;
-    if (last_ms) {
-        last_ms[0] = t->match_ms[0];
-        last_ms[1] = t->match_ms[1];
-    }
-    return LBA_OK;
+    return t ? t->match_timer.profile(on, last_ms, 2) : LBA_E_ARG;
 }
 
 extern "C" int lba_match_project(lba_tracker* t, lba_match_search* searches, int32_t n_searches, lba_match_cam* cams,
@@ -278,43 +270,32 @@ extern "C" int lba_match_project(lba_tracker* t, lba_match_search* searches, int
     if (n_searches == 0) return LBA_OK;
     // ---- the arena: inputs (one upload), outputs (one download), work; the pinned image covers inputs and outputs
     const size_t nj = (size_t)n_jobs, nf = (size_t)n_feats;
-    ArenaLayout lay;
-    const size_t o_searches = lay.take((size_t)n_searches * sizeof(lba_match_search));
-    const size_t o_cams = lay.take((size_t)n_cams * sizeof(lba_match_cam));
-    const size_t o_cs = lay.take((size_t)n_cell_start * sizeof(int32_t));
-    const size_t o_cf = lay.take((size_t)n_cell_feat * sizeof(int32_t));
-    const size_t o_feats = lay.take(nf * sizeof(lba_match_feat));
-    const size_t o_jobs = lay.take(nj * sizeof(lba_match_job));
-    const size_t o_jsearch = lay.take(nj * sizeof(int));
-    const size_t o_flocal = lay.take(nf * sizeof(int));
-    const size_t o_loff = lay.take((nj + 1) * sizeof(unsigned));
-    const size_t o_camrec = lay.take(n_camrec * sizeof(MatchCamRec));
-    const size_t o_cjobs = lay.take(nj * sizeof(int));
-    const size_t o_cfeats = lay.take(nf * sizeof(int));
-    const size_t out0 = lay.total;
-    const size_t o_status = lay.take(4 * nj * sizeof(int));
-    const size_t o_fjob = lay.take(nf * sizeof(int));
-    const size_t o_rounds = lay.take(n_camrec * sizeof(int));
-    const size_t out1 = lay.total;
-    const size_t o_ncand = lay.take(nj * sizeof(int));
-    if (lay.total > (size_t(1) << 31)) MATCH_REFUSE(LBA_E_LIMIT, "lba_match_project: the batch exceeds 2 GB");
+    ArenaPlan plan;
+    const Sec<lba_match_search> o_searches = plan.in<lba_match_search>((size_t)n_searches);
+    const Sec<lba_match_cam> o_cams = plan.in<lba_match_cam>((size_t)n_cams);
+    const Sec<int32_t> o_cs = plan.in<int32_t>((size_t)n_cell_start), o_cf = plan.in<int32_t>((size_t)n_cell_feat);
+    const Sec<lba_match_feat> o_feats = plan.in<lba_match_feat>(nf);
+    const Sec<lba_match_job> o_jobs = plan.in<lba_match_job>(nj);
+    const Sec<int> o_jsearch = plan.in<int>(nj), o_flocal = plan.in<int>(nf);
+    const Sec<unsigned> o_loff = plan.in<unsigned>(nj + 1);
+    const Sec<MatchCamRec> o_camrec = plan.in<MatchCamRec>(n_camrec);
+    const Sec<int> o_cjobs = plan.in<int>(nj), o_cfeats = plan.in<int>(nf);
+    const Sec<int> o_status = plan.out<int>(4 * nj), o_fjob = plan.out<int>(nf), o_rounds = plan.out<int>(n_camrec);
+    const Sec<int> o_ncand = plan.work<int>(nj);
+    if (plan.over_2gb()) MATCH_REFUSE(LBA_E_LIMIT, "lba_match_project: the batch exceeds 2 GB");
     char* h = nullptr;
     try {
-        TR_HIP(hipSetDevice(t->cfg.device));
-        grow_bytes(t->h_sim3, t->sim3_pin_cap, out1, out1 * 2, true);
-        h = t->h_sim3;
-        std::memcpy(h + o_searches, searches, (size_t)n_searches * sizeof(lba_match_search));
-        if (n_cams) std::memcpy(h + o_cams, cams, (size_t)n_cams * sizeof(lba_match_cam));
-        if (n_cell_start) std::memcpy(h + o_cs, cell_start, (size_t)n_cell_start * sizeof(int32_t));
-        if (n_cell_feat) std::memcpy(h + o_cf, cell_feat, (size_t)n_cell_feat * sizeof(int32_t));
-        if (nf) std::memcpy(h + o_feats, feats, nf * sizeof(lba_match_feat));
-        if (nj) std::memcpy(h + o_jobs, jobs, nj * sizeof(lba_match_job));
-        int* jsearch = reinterpret_cast<int*>(h + o_jsearch);
-        int* flocal = reinterpret_cast<int*>(h + o_flocal);
-        unsigned* loff = reinterpret_cast<unsigned*>(h + o_loff);
-        MatchCamRec* camrec = reinterpret_cast<MatchCamRec*>(h + o_camrec);
-        int* cjobs = reinterpret_cast<int*>(h + o_cjobs);
-        int* cfeats = reinterpret_cast<int*>(h + o_cfeats);
+        ArenaCall call{t, plan, t->match_timer};
+        h = call.pin();
+        std::memcpy(o_searches.at(h), searches, (size_t)n_searches * sizeof(lba_match_search));
+        if (n_cams) std::memcpy(o_cams.at(h), cams, (size_t)n_cams * sizeof(lba_match_cam));
+        if (n_cell_start) std::memcpy(o_cs.at(h), cell_start, (size_t)n_cell_start * sizeof(int32_t));
+        if (n_cell_feat) std::memcpy(o_cf.at(h), cell_feat, (size_t)n_cell_feat * sizeof(int32_t));
+        if (nf) std::memcpy(o_feats.at(h), feats, nf * sizeof(lba_match_feat));
+        if (nj) std::memcpy(o_jobs.at(h), jobs, nj * sizeof(lba_match_job));
+        int *jsearch = o_jsearch.at(h), *flocal = o_flocal.at(h), *cjobs = o_cjobs.at(h), *cfeats = o_cfeats.at(h);
+        unsigned* loff = o_loff.at(h);
+        MatchCamRec* camrec = o_camrec.at(h);
         for (size_t g = 0; g < nj; ++g) jsearch[g] = -1;
         for (size_t g = 0; g <= nj; ++g) loff[g] = 0;   // capacities first, offsets by the prefix sum below
         for (size_t f = 0; f < nf; ++f) flocal[f] = 0;
@@ -351,60 +332,36 @@ extern "C" int lba_match_project(lba_tracker* t, lba_match_search* searches, int
             if (total > 0x7fffffffu) throw TrackerError{LBA_E_LIMIT, "lba_match_project: the batch exceeds 2 GB"};
             loff[g + 1] = (unsigned)total;
         }
-        const size_t o_cand = lay.take((size_t)total * sizeof(uint32_t));
-        if (lay.total > (size_t(1) << 31)) throw TrackerError{LBA_E_LIMIT, "lba_match_project: the batch exceeds 2 GB"};
-        grow_bytes(t->d_arena, t->arena_cap, lay.total, lay.total * 2);
-        char* d = t->d_arena;
-        hipStream_t st = t->stream;
-        if (t->match_timed && !t->match_ev[0])
-            for (hipEvent_t& e : t->match_ev) TR_HIP(hipEventCreate(&e));
-        TR_HIP(hipMemcpyAsync(d, h, out0, hipMemcpyHostToDevice, st));
+        // the candidate lists: their size is known only now, from the filled image
+        const Sec<uint32_t> o_cand = plan.work<uint32_t>((size_t)total);
+        if (plan.over_2gb()) throw TrackerError{LBA_E_LIMIT, "lba_match_project: the batch exceeds 2 GB"};
+        char* d = call.place();
+        call.upload();
         MatchArgs a;
-        a.searches = reinterpret_cast<const lba_match_search*>(d + o_searches);
-        a.cams = reinterpret_cast<const lba_match_cam*>(d + o_cams);
-        a.cell_start = reinterpret_cast<const int*>(d + o_cs);
-        a.cell_feat = reinterpret_cast<const int*>(d + o_cf);
-        a.feats = reinterpret_cast<const lba_match_feat*>(d + o_feats);
-        a.jobs = reinterpret_cast<const lba_match_job*>(d + o_jobs);
-        a.job_search = reinterpret_cast<const int*>(d + o_jsearch);
-        a.feat_local = reinterpret_cast<const int*>(d + o_flocal);
-        a.list_off = reinterpret_cast<const unsigned*>(d + o_loff);
-        a.camrec = reinterpret_cast<const MatchCamRec*>(d + o_camrec);
-        a.cam_jobs = reinterpret_cast<const int*>(d + o_cjobs);
-        a.cam_feats = reinterpret_cast<const int*>(d + o_cfeats);
-        a.cand = reinterpret_cast<uint32_t*>(d + o_cand);
-        a.n_cand = reinterpret_cast<int*>(d + o_ncand);
-        a.status = reinterpret_cast<int*>(d + o_status);
-        a.feat_job = reinterpret_cast<int*>(d + o_fjob);
-        a.rounds = reinterpret_cast<int*>(d + o_rounds);
+        a.searches = o_searches.at(d); a.cams = o_cams.at(d); a.cell_start = o_cs.at(d); a.cell_feat = o_cf.at(d);
+        a.feats = o_feats.at(d); a.jobs = o_jobs.at(d); a.job_search = o_jsearch.at(d); a.feat_local = o_flocal.at(d);
+        a.list_off = o_loff.at(d); a.camrec = o_camrec.at(d); a.cam_jobs = o_cjobs.at(d); a.cam_feats = o_cfeats.at(d);
+        a.cand = o_cand.at(d); a.n_cand = o_ncand.at(d);
+        a.status = o_status.at(d); a.feat_job = o_fjob.at(d); a.rounds = o_rounds.at(d);
         a.n_jobs = n_jobs;
         a.mode = P.mode; a.th_high = P.th_high; a.stereo_cam = P.stereo_cam; a.ur_truncate = P.ur_truncate;
         a.nn_ratio = P.nn_ratio;
-        if (t->match_timed) TR_HIP(hipEventRecord(t->match_ev[0], st));
+        hipStream_t st = t->stream;
+        call.mark();
         if (n_jobs) {
             hipLaunchKernelGGL(k_match_gather, dim3((unsigned)n_jobs), dim3(MG_WG), 0, st, a);
             TR_HIP(hipGetLastError());
         }
-        if (t->match_timed) TR_HIP(hipEventRecord(t->match_ev[1], st));
+        call.mark();
         hipLaunchKernelGGL(k_match_resolve, dim3((unsigned)n_camrec), dim3(MR_WG), 0, st, a);
         TR_HIP(hipGetLastError());
-        if (t->match_timed) TR_HIP(hipEventRecord(t->match_ev[2], st));
-        TR_HIP(hipMemcpyAsync(h + out0, d + out0, out1 - out0, hipMemcpyDeviceToHost, st));
-        TR_HIP(hipStreamSynchronize(st));
-        if (t->match_timed) {
-            float ms0 = -1.f, ms1 = -1.f;
-            TR_HIP(hipEventElapsedTime(&ms0, t->match_ev[0], t->match_ev[1]));
-            TR_HIP(hipEventElapsedTime(&ms1, t->match_ev[1], t->match_ev[2]));
-            t->match_ms[0] = ms0;
-            t->match_ms[1] = ms1;
-        }
+        call.mark();
+        call.finish();
     } catch (const TrackerError& e) {
         return tracker_fail(t, e);
     }
     // ---- scatter: the jobs' and features' outputs, the cameras' rounds; then the rotation pass and the counts
-    const int* r_status = reinterpret_cast<const int*>(h + o_status);
-    const int* r_fjob = reinterpret_cast<const int*>(h + o_fjob);
-    const int* r_rounds = reinterpret_cast<const int*>(h + o_rounds);
+    const int *r_status = o_status.at(h), *r_fjob = o_fjob.at(h), *r_rounds = o_rounds.at(h);
     size_t r = 0;
     for (int s = 0; s < n_searches; ++s) {
         lba_match_search& S = searches[s];

@@ -498,43 +498,44 @@ void pg_upload(lba_tracker* t, const lba_pg_vertex* v, const lba_pg_edge* e, int
         joff.push_back(j.off);
     }
     pg_pack_state(v, G.n_v, R.h_state);
-    const size_t o_ed = in.put(ed);
-    const size_t o_S = in.put(R.h_state);
-    const size_t o_voff = in.put(G.voff), o_vslot = in.put(G.slot);
-    const size_t o_jptr = in.put(G.job_ptr), o_jflag = in.put(jflag), o_jtile = in.put(jtile), o_joff = in.put(joff);
-    const size_t o_con = in.put(G.contrib);
-    const size_t o_lvl = in.put(G.lvl_cols), o_dt = in.put(G.diag_tile), o_rkp = in.put(G.rk_ptr), o_rkt = in.put(G.rk_tile);
-    const size_t o_rkc = in.put(G.rk_col), o_crp = in.put(G.cr_ptr), o_crt = in.put(G.cr_tile), o_crr = in.put(G.cr_row);
-    const size_t o_prp = in.put(G.pr_ptr), o_pra = in.put(G.pr_a), o_prb = in.put(G.pr_b);
+    const Sec<lba_pg_edge> o_ed = in.put(ed);
+    const Sec<double> o_S = in.put(R.h_state);
+    const Sec<int> o_voff = in.put(G.voff), o_vslot = in.put(G.slot);
+    const Sec<int> o_jptr = in.put(G.job_ptr), o_jflag = in.put(jflag), o_jtile = in.put(jtile), o_joff = in.put(joff);
+    const Sec<int> o_con = in.put(G.contrib);
+    const Sec<int> o_lvl = in.put(G.lvl_cols), o_dt = in.put(G.diag_tile), o_rkp = in.put(G.rk_ptr), o_rkt = in.put(G.rk_tile);
+    const Sec<int> o_rkc = in.put(G.rk_col), o_crp = in.put(G.cr_ptr), o_crt = in.put(G.cr_tile), o_crr = in.put(G.cr_row);
+    const Sec<int> o_prp = in.put(G.pr_ptr), o_pra = in.put(G.pr_a), o_prb = in.put(G.pr_b);
     const size_t up = A.total;
-    const size_t o_T = A.take((size_t)G.n_v * 8 * sizeof(double));
-    const size_t o_err = A.take((size_t)ne * 7 * sizeof(double)), o_J = A.take((size_t)ne * 98 * sizeof(double));
-    const size_t o_chi = A.take((size_t)ne * sizeof(double));
-    const size_t o_tiles = A.take((size_t)nt * PG_TILE * sizeof(double));
-    const size_t o_dinv = A.take((size_t)NP * PG_TILE * sizeof(double));
-    const size_t vec = (size_t)NP * PG_NB * sizeof(double);
-    const size_t o_b = A.take(vec), o_hd = A.take(vec), o_y = A.take(vec), o_x = A.take(vec);
-    const size_t o_dx = A.take((size_t)G.na * 7 * sizeof(double));
-    const size_t o_out = A.take(4 * sizeof(double)), o_fail = A.take(sizeof(int));
+    const Sec<double> o_T = A.take<double>((size_t)G.n_v * 8);
+    const Sec<double> o_err = A.take<double>((size_t)ne * 7), o_J = A.take<double>((size_t)ne * 98);
+    const Sec<double> o_chi = A.take<double>((size_t)ne);
+    const Sec<double> o_tiles = A.take<double>((size_t)nt * PG_TILE);
+    const Sec<double> o_dinv = A.take<double>((size_t)NP * PG_TILE);
+    const size_t vec = (size_t)NP * PG_NB;
+    const Sec<double> o_b = A.take<double>(vec), o_hd = A.take<double>(vec), o_y = A.take<double>(vec), o_x = A.take<double>(vec);
+    const Sec<double> o_dx = A.take<double>((size_t)G.na * 7);
+    const Sec<double> o_out = A.take<double>(4);
+    const Sec<int> o_fail = A.take<int>(1);
     if (A.total > PG_MAX_BYTES) throw TrackerError{LBA_E_LIMIT, "the pose graph's factor exceeds 6 GB of device memory"};
     TR_HIP(hipSetDevice(t->cfg.device));
     grow_bytes(t->d_arena, t->arena_cap, A.total, A.total + A.total / 2);
     char* d = t->d_arena;
     TR_HIP(hipMemcpyAsync(d, in.bytes.data(), up, hipMemcpyHostToDevice, t->stream));
     TR_HIP(hipStreamSynchronize(t->stream));   // (the image is pageable and goes out of scope)
-    auto ip = [&](size_t o) { return reinterpret_cast<const int*>(d + o); };
-    auto dp = [&](size_t o) { return reinterpret_cast<double*>(d + o); };
     PgDev& D = R.D;
-    D.edges = reinterpret_cast<const lba_pg_edge*>(d + o_ed);
+    D.edges = o_ed.at(d);
     D.ne = ne; D.nv = G.n_v; D.NP = NP; D.fix_scale = fix_scale != 0;
-    D.voff = ip(o_voff); D.vslot = ip(o_vslot);
-    D.job_ptr = ip(o_jptr); D.job_flag = ip(o_jflag); D.job_tile = ip(o_jtile); D.job_off = ip(o_joff); D.contrib = ip(o_con);
-    D.lvl_cols = ip(o_lvl); D.diag_tile = ip(o_dt); D.rk_ptr = ip(o_rkp); D.rk_tile = ip(o_rkt); D.rk_col = ip(o_rkc);
-    D.cr_ptr = ip(o_crp); D.cr_tile = ip(o_crt); D.cr_row = ip(o_crr); D.pr_ptr = ip(o_prp); D.pr_a = ip(o_pra); D.pr_b = ip(o_prb);
-    D.err = dp(o_err); D.J = dp(o_J); D.chi = dp(o_chi); D.tiles = dp(o_tiles); D.dinv = dp(o_dinv);
-    D.b = dp(o_b); D.hdiag = dp(o_hd); D.y = dp(o_y); D.x = dp(o_x); D.dxnat = dp(o_dx); D.out = dp(o_out);
-    D.fail = reinterpret_cast<int*>(d + o_fail);
-    R.t = t; R.S = dp(o_S); R.T = dp(o_T);
+    D.voff = o_voff.at(d); D.vslot = o_vslot.at(d);
+    D.job_ptr = o_jptr.at(d); D.job_flag = o_jflag.at(d); D.job_tile = o_jtile.at(d); D.job_off = o_joff.at(d);
+    D.contrib = o_con.at(d);
+    D.lvl_cols = o_lvl.at(d); D.diag_tile = o_dt.at(d); D.rk_ptr = o_rkp.at(d); D.rk_tile = o_rkt.at(d); D.rk_col = o_rkc.at(d);
+    D.cr_ptr = o_crp.at(d); D.cr_tile = o_crt.at(d); D.cr_row = o_crr.at(d);
+    D.pr_ptr = o_prp.at(d); D.pr_a = o_pra.at(d); D.pr_b = o_prb.at(d);
+    D.err = o_err.at(d); D.J = o_J.at(d); D.chi = o_chi.at(d); D.tiles = o_tiles.at(d); D.dinv = o_dinv.at(d);
+    D.b = o_b.at(d); D.hdiag = o_hd.at(d); D.y = o_y.at(d); D.x = o_x.at(d); D.dxnat = o_dx.at(d); D.out = o_out.at(d);
+    D.fail = o_fail.at(d);
+    R.t = t; R.S = o_S.at(d); R.T = o_T.at(d);
     R.njobs = (int)G.jobs.size(); R.nlevel = G.nlevel; R.G = &G;
 }
 

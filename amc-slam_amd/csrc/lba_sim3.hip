@@ -284,10 +284,7 @@ __global__ __launch_bounds__(S3_WAVE) void k_sim3(S3Args A) {
 }  // namespace
 
 extern "C" int lba_sim3_profile(lba_tracker* t, int32_t on, double* last_ms) {
-    if (!t) return LBA_E_ARG;
-    t->sim3_timed = on != 0;
-    if (last_ms) *last_ms = t->sim3_ms;
-    return LBA_OK;
+    return t ? t->sim3_timer.profile(on, last_ms, 1) : LBA_E_ARG;
 }
 
 extern "C" int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n_pairs, lba_sim3_corr* corr, int32_t n_corr,
@@ -313,24 +310,19 @@ extern "C" int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n
     const size_t lds = sizeof(double) * (2 * (size_t)n_cam * CAMD_N + (size_t)S3_FIELDS * stride) + sizeof(int) * 3 * (size_t)stride;
     if (lds > S3_LDS_MAX) return tracker_fail(t, {LBA_E_LIMIT, "a pair's correspondences and cameras exceed 64 KB of LDS"});
     // ---- the arena: inputs (one upload), outputs (one download); its pinned host image has the same offsets
-    ArenaLayout lay;
-    const size_t o_pairs = lay.take((size_t)n_pairs * sizeof(S3Pair));
-    const size_t o_rows = lay.take(n_rows * sizeof(lba_sim3_corr));
-    const size_t o_cams = lay.take((size_t)n_cam_rows * sizeof(lba_sim3_cam));
-    const size_t out0 = lay.total;
-    const size_t o_state = lay.take((size_t)n_pairs * 8 * sizeof(double));
-    const size_t o_info = lay.take((size_t)n_pairs * 4 * sizeof(int));
-    const size_t o_flag = lay.take(n_rows * sizeof(int));
-    const size_t total = lay.total;
+    ArenaPlan plan;
+    const Sec<S3Pair> o_pairs = plan.in<S3Pair>((size_t)n_pairs);
+    const Sec<lba_sim3_corr> o_rows = plan.in<lba_sim3_corr>(n_rows);
+    const Sec<lba_sim3_cam> o_cams = plan.in<lba_sim3_cam>((size_t)n_cam_rows);
+    const Sec<double> o_state = plan.out<double>((size_t)n_pairs * 8);
+    const Sec<int> o_info = plan.out<int>((size_t)n_pairs * 4), o_flag = plan.out<int>(n_rows);
     char* h = nullptr;
     try {
-        TR_HIP(hipSetDevice(t->cfg.device));
-        grow_bytes(t->d_arena, t->arena_cap, total, total * 2);
-        grow_bytes(t->h_sim3, t->sim3_pin_cap, total, total * 2, true);
-        h = t->h_sim3;
+        ArenaCall call{t, plan, t->sim3_timer};
+        h = call.pin();
         // per pair: its rows packed in pair order (overlapping ranges get rows of their own)
-        S3Pair* sp = reinterpret_cast<S3Pair*>(h + o_pairs);
-        lba_sim3_corr* rows = reinterpret_cast<lba_sim3_corr*>(h + o_rows);
+        S3Pair* sp = o_pairs.at(h);
+        lba_sim3_corr* rows = o_rows.at(h);
         size_t row0 = 0;
         for (int p = 0; p < n_pairs; ++p) {
             const lba_sim3_pair& P = pairs[p];
@@ -347,39 +339,25 @@ extern "C" int lba_sim3_optimize(lba_tracker* t, lba_sim3_pair* pairs, int32_t n
             if (P.n_corr) std::memcpy(rows + row0, corr + P.corr0, (size_t)P.n_corr * sizeof(lba_sim3_corr));
             row0 += (size_t)P.n_corr;
         }
-        std::memcpy(h + o_cams, cams, (size_t)n_cam_rows * sizeof(lba_sim3_cam));
-        char* d = t->d_arena;
-        hipStream_t s = t->stream;
-        if (t->sim3_timed && !t->sim3_ev[0])
-            for (hipEvent_t& e : t->sim3_ev) TR_HIP(hipEventCreate(&e));
-        TR_HIP(hipMemcpyAsync(d, h, out0, hipMemcpyHostToDevice, s));
+        std::memcpy(o_cams.at(h), cams, (size_t)n_cam_rows * sizeof(lba_sim3_cam));
+        char* d = call.place();
+        call.upload();
         S3Args a;
-        a.pairs = reinterpret_cast<const S3Pair*>(d + o_pairs);
-        a.corr = reinterpret_cast<const lba_sim3_corr*>(d + o_rows);
-        a.cams = reinterpret_cast<const lba_sim3_cam*>(d + o_cams);
-        a.state = reinterpret_cast<double*>(d + o_state);
-        a.info = reinterpret_cast<int*>(d + o_info);
-        a.flag = reinterpret_cast<int*>(d + o_flag);
+        a.pairs = o_pairs.at(d); a.corr = o_rows.at(d); a.cams = o_cams.at(d);
+        a.state = o_state.at(d); a.info = o_info.at(d); a.flag = o_flag.at(d);
         a.tau = t->cfg.tau; a.max_trials = t->cfg.max_trials; a.early_stop = t->cfg.early_stop;
         a.n_cam = n_cam; a.stride = stride;
-        if (t->sim3_timed) TR_HIP(hipEventRecord(t->sim3_ev[0], s));
-        hipLaunchKernelGGL(k_sim3, dim3((unsigned)n_pairs), dim3(S3_WAVE), lds, s, a);
+        call.mark();
+        hipLaunchKernelGGL(k_sim3, dim3((unsigned)n_pairs), dim3(S3_WAVE), lds, t->stream, a);
         TR_HIP(hipGetLastError());
-        if (t->sim3_timed) TR_HIP(hipEventRecord(t->sim3_ev[1], s));
-        TR_HIP(hipMemcpyAsync(h + out0, d + out0, total - out0, hipMemcpyDeviceToHost, s));
-        TR_HIP(hipStreamSynchronize(s));
-        if (t->sim3_timed) {
-            float ms = -1.f;
-            TR_HIP(hipEventElapsedTime(&ms, t->sim3_ev[0], t->sim3_ev[1]));
-            t->sim3_ms = ms;
-        }
+        call.mark();
+        call.finish();
     } catch (const TrackerError& e) {
         return tracker_fail(t, e);
     }
-    const S3Pair* sp = reinterpret_cast<const S3Pair*>(h + o_pairs);
-    const double* r_state = reinterpret_cast<const double*>(h + o_state);
-    const int* r_info = reinterpret_cast<const int*>(h + o_info);
-    const int* r_flag = reinterpret_cast<const int*>(h + o_flag);
+    const S3Pair* sp = o_pairs.at(h);
+    const double* r_state = o_state.at(h);
+    const int *r_info = o_info.at(h), *r_flag = o_flag.at(h);
     for (int p = 0; p < n_pairs; ++p) {
         lba_sim3_pair& P = pairs[p];
         const int* io = r_info + (size_t)p * 4;

@@ -158,10 +158,7 @@ __global__ __launch_bounds__(S3R_WAVE) void k_s3r_select(S3RArgs A) {
 }  // namespace
 
 extern "C" int lba_sim3_ransac_profile(lba_tracker* t, int32_t on, double* last_ms) {
-    if (!t) return LBA_E_ARG;
-    t->s3r_timed = on != 0;
-    if (last_ms) *last_ms = t->s3r_ms;
-    return LBA_OK;
+    return t ? t->s3r_timer.profile(on, last_ms, 1) : LBA_E_ARG;
 }
 
 extern "C" int lba_sim3_ransac(lba_tracker* t, lba_s3r_pair* pairs, int32_t n_pairs, lba_s3r_corr* corr, int32_t n_corr,
@@ -198,34 +195,26 @@ extern "C" int lba_sim3_ransac(lba_tracker* t, lba_s3r_pair* pairs, int32_t n_pa
     }
     // ---- the arena: inputs (one upload), outputs (one download), masks (device only); its pinned host image has
     // the same offsets
-    ArenaLayout lay;
-    const size_t o_pairs = lay.take((size_t)n_pairs * sizeof(S3RPair));
-    const size_t o_rows = lay.take(n_rows * sizeof(lba_s3r_corr));
-    const size_t o_cams = lay.take((size_t)n_cam_rows * sizeof(lba_sim3_cam));
-    const size_t o_tri = lay.take(n_work * 3 * sizeof(int));
-    const size_t o_work = lay.take(n_work * sizeof(int));
-    const size_t out0 = lay.total;
-    const size_t o_hS = lay.take(n_work * 8 * sizeof(double));
-    const size_t o_hinl = lay.take(n_work * sizeof(int));
-    const size_t o_hflag = lay.take(n_work * sizeof(int));
-    const size_t o_state = lay.take((size_t)n_pairs * 8 * sizeof(double));
-    const size_t o_info = lay.take((size_t)n_pairs * 4 * sizeof(int));
-    const size_t o_inl = lay.take(n_rows * sizeof(int));
-    const size_t out1 = lay.total;
-    const size_t o_mask = lay.take((size_t)words * sizeof(unsigned long long));
-    if (n_rows > 0x7fffffff || n_work > 0x7fffffff || lay.total > (size_t(1) << 31))
+    ArenaPlan plan;
+    const Sec<S3RPair> o_pairs = plan.in<S3RPair>((size_t)n_pairs);
+    const Sec<lba_s3r_corr> o_rows = plan.in<lba_s3r_corr>(n_rows);
+    const Sec<lba_sim3_cam> o_cams = plan.in<lba_sim3_cam>((size_t)n_cam_rows);
+    const Sec<int> o_tri = plan.in<int>(n_work * 3), o_work = plan.in<int>(n_work);
+    const Sec<double> o_hS = plan.out<double>(n_work * 8);
+    const Sec<int> o_hinl = plan.out<int>(n_work), o_hflag = plan.out<int>(n_work);
+    const Sec<double> o_state = plan.out<double>((size_t)n_pairs * 8);
+    const Sec<int> o_info = plan.out<int>((size_t)n_pairs * 4), o_inl = plan.out<int>(n_rows);
+    const Sec<unsigned long long> o_mask = plan.work<unsigned long long>((size_t)words);
+    if (n_rows > 0x7fffffff || n_work > 0x7fffffff || plan.over_2gb())
         return tracker_fail(t, {LBA_E_LIMIT, "the batch's rows, hypotheses and inlier masks exceed 2 GB"});
     char* h = nullptr;
     try {
-        TR_HIP(hipSetDevice(t->cfg.device));
-        grow_bytes(t->d_arena, t->arena_cap, lay.total, lay.total * 2);
-        grow_bytes(t->h_sim3, t->sim3_pin_cap, out1, out1 * 2, true);
-        h = t->h_sim3;
+        ArenaCall call{t, plan, t->s3r_timer};
+        h = call.pin();
         // per pair: its rows packed in pair order (overlapping ranges get rows of their own), its triples as work items
-        S3RPair* sp = reinterpret_cast<S3RPair*>(h + o_pairs);
-        lba_s3r_corr* rows = reinterpret_cast<lba_s3r_corr*>(h + o_rows);
-        int* tri = reinterpret_cast<int*>(h + o_tri);
-        int* work_pair = reinterpret_cast<int*>(h + o_work);
+        S3RPair* sp = o_pairs.at(h);
+        lba_s3r_corr* rows = o_rows.at(h);
+        int *tri = o_tri.at(h), *work_pair = o_work.at(h);
         size_t row0 = 0, work0 = 0;
         long long mask0 = 0;
         for (int p = 0; p < n_pairs; ++p) {
@@ -244,49 +233,30 @@ extern "C" int lba_sim3_ransac(lba_tracker* t, lba_s3r_pair* pairs, int32_t n_pa
             work0 += (size_t)P.n_hyp;
             mask0 += (long long)P.n_hyp * D.words;
         }
-        std::memcpy(h + o_cams, cams, (size_t)n_cam_rows * sizeof(lba_sim3_cam));
-        char* d = t->d_arena;
-        hipStream_t s = t->stream;
-        if (t->s3r_timed && !t->sim3_ev[0])
-            for (hipEvent_t& e : t->sim3_ev) TR_HIP(hipEventCreate(&e));
-        TR_HIP(hipMemcpyAsync(d, h, out0, hipMemcpyHostToDevice, s));
+        std::memcpy(o_cams.at(h), cams, (size_t)n_cam_rows * sizeof(lba_sim3_cam));
+        char* d = call.place();
+        call.upload();
         S3RArgs a;
-        a.pairs = reinterpret_cast<const S3RPair*>(d + o_pairs);
-        a.corr = reinterpret_cast<const lba_s3r_corr*>(d + o_rows);
-        a.cams = reinterpret_cast<const lba_sim3_cam*>(d + o_cams);
-        a.tri = reinterpret_cast<const int*>(d + o_tri);
-        a.work_pair = reinterpret_cast<const int*>(d + o_work);
-        a.hyp_S12 = reinterpret_cast<double*>(d + o_hS);
-        a.hyp_inl = reinterpret_cast<int*>(d + o_hinl);
-        a.hyp_flag = reinterpret_cast<int*>(d + o_hflag);
-        a.state = reinterpret_cast<double*>(d + o_state);
-        a.info = reinterpret_cast<int*>(d + o_info);
-        a.inlier = reinterpret_cast<int*>(d + o_inl);
-        a.mask = reinterpret_cast<unsigned long long*>(d + o_mask);
+        a.pairs = o_pairs.at(d); a.corr = o_rows.at(d); a.cams = o_cams.at(d);
+        a.tri = o_tri.at(d); a.work_pair = o_work.at(d);
+        a.hyp_S12 = o_hS.at(d); a.hyp_inl = o_hinl.at(d); a.hyp_flag = o_hflag.at(d);
+        a.state = o_state.at(d); a.info = o_info.at(d); a.inlier = o_inl.at(d);
+        a.mask = o_mask.at(d);
         a.n_cam = n_cam;
         const size_t lds = sizeof(double) * 2 * (size_t)n_cam * CAMD_N;
-        if (t->s3r_timed) TR_HIP(hipEventRecord(t->sim3_ev[0], s));
+        hipStream_t s = t->stream;
+        call.mark();
         if (n_work) hipLaunchKernelGGL(k_s3r_hyp, dim3((unsigned)n_work), dim3(S3R_WAVE), lds, s, a);
         hipLaunchKernelGGL(k_s3r_select, dim3((unsigned)n_pairs), dim3(S3R_WAVE), 0, s, a);
         TR_HIP(hipGetLastError());
-        if (t->s3r_timed) TR_HIP(hipEventRecord(t->sim3_ev[1], s));
-        TR_HIP(hipMemcpyAsync(h + out0, d + out0, out1 - out0, hipMemcpyDeviceToHost, s));
-        TR_HIP(hipStreamSynchronize(s));
-        if (t->s3r_timed) {
-            float ms = -1.f;
-            TR_HIP(hipEventElapsedTime(&ms, t->sim3_ev[0], t->sim3_ev[1]));
-            t->s3r_ms = ms;
-        }
+        call.mark();
+        call.finish();
     } catch (const TrackerError& e) {
         return tracker_fail(t, e);
     }
-    const S3RPair* sp = reinterpret_cast<const S3RPair*>(h + o_pairs);
-    const double* r_hS = reinterpret_cast<const double*>(h + o_hS);
-    const int* r_hinl = reinterpret_cast<const int*>(h + o_hinl);
-    const int* r_hflag = reinterpret_cast<const int*>(h + o_hflag);
-    const double* r_state = reinterpret_cast<const double*>(h + o_state);
-    const int* r_info = reinterpret_cast<const int*>(h + o_info);
-    const int* r_inl = reinterpret_cast<const int*>(h + o_inl);
+    const S3RPair* sp = o_pairs.at(h);
+    const double *r_hS = o_hS.at(h), *r_state = o_state.at(h);
+    const int *r_hinl = o_hinl.at(h), *r_hflag = o_hflag.at(h), *r_info = o_info.at(h), *r_inl = o_inl.at(h);
     for (int p = 0; p < n_pairs; ++p) {
         lba_s3r_pair& P = pairs[p];
         const S3RPair& D = sp[p];

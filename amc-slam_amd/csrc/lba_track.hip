@@ -495,6 +495,8 @@ void lba_tracker_destroy(lba_tracker* t) {
     delete t;   // frees the buffers and the events
 }
 
+const char* lba_tracker_last_error(const lba_tracker* t) { return t ? t->err.c_str() : "null tracker"; }
+
 int lba_track(lba_tracker* t, lba_track_frame* frames, int32_t n_frames, lba_track_obs* obs, int32_t n_obs,
               const lba_cam* cams, int32_t n_cam) {
     if (!t || n_frames < 0 || n_obs < 0 || (n_frames && !frames) || (n_obs && !obs) || n_cam < 1 || !cams)

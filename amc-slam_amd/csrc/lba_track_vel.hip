@@ -262,20 +262,19 @@ extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32
     const size_t n_work = work_frame.size();
     // ---- the arena: inputs (one upload), outputs (one download), masks (device only)
     ArenaImage in;
-    const size_t o_frames = in.put(vf);
-    const size_t o_obs = in.put(obs, (size_t)n_obs);
-    const size_t o_obs_smp = in.put(obs_smp), o_smp_dt = in.put(smp_dt), o_tri = in.put(tri);
-    const size_t o_work = in.put(work_frame), o_camd = in.put(camd_pack(cams, n_cam));
+    const Sec<VelFrame> o_frames = in.put(vf);
+    const Sec<lba_vel_obs> o_obs = in.put(obs, (size_t)n_obs);
+    const Sec<int> o_obs_smp = in.put(obs_smp);
+    const Sec<double> o_smp_dt = in.put(smp_dt);
+    const Sec<int> o_tri = in.put(tri), o_work = in.put(work_frame);
+    const Sec<double> o_camd = in.put(camd_pack(cams, n_cam));
     ArenaLayout& lay = in.lay;
     const size_t out0 = lay.total;
-    const size_t o_hvel = lay.take(n_work * 6 * sizeof(double));
-    const size_t o_fvel = lay.take((size_t)n_frames * 6 * sizeof(double));
-    const size_t o_hinl = lay.take(n_work * sizeof(int));
-    const size_t o_hit = lay.take(n_work * sizeof(int));
-    const size_t o_best = lay.take((size_t)n_frames * 2 * sizeof(int));
-    const size_t o_inl = lay.take((size_t)rows * sizeof(int));
+    const Sec<double> o_hvel = lay.take<double>(n_work * 6), o_fvel = lay.take<double>((size_t)n_frames * 6);
+    const Sec<int> o_hinl = lay.take<int>(n_work), o_hit = lay.take<int>(n_work);
+    const Sec<int> o_best = lay.take<int>((size_t)n_frames * 2), o_inl = lay.take<int>((size_t)rows);
     const size_t out1 = lay.total;
-    const size_t o_mask = lay.take((size_t)words * sizeof(unsigned long long));
+    const Sec<unsigned long long> o_mask = lay.take<unsigned long long>((size_t)words);
     std::vector<char> out(out1 - out0);
     try {
         TR_HIP(hipSetDevice(t->cfg.device));
@@ -284,20 +283,10 @@ extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32
         hipStream_t s = t->stream;
         TR_HIP(hipMemcpyAsync(d, in.bytes.data(), in.bytes.size(), hipMemcpyHostToDevice, s));
         VelArgs a;
-        a.frames = reinterpret_cast<const VelFrame*>(d + o_frames);
-        a.obs = reinterpret_cast<const lba_vel_obs*>(d + o_obs);
-        a.obs_smp = reinterpret_cast<const int*>(d + o_obs_smp);
-        a.smp_dt = reinterpret_cast<const double*>(d + o_smp_dt);
-        a.tri = reinterpret_cast<const int*>(d + o_tri);
-        a.work_frame = reinterpret_cast<const int*>(d + o_work);
-        a.camd = reinterpret_cast<const double*>(d + o_camd);
-        a.hyp_vel = reinterpret_cast<double*>(d + o_hvel);
-        a.frame_vel = reinterpret_cast<double*>(d + o_fvel);
-        a.hyp_inl = reinterpret_cast<int*>(d + o_hinl);
-        a.hyp_it = reinterpret_cast<int*>(d + o_hit);
-        a.frame_best = reinterpret_cast<int*>(d + o_best);
-        a.inlier = reinterpret_cast<int*>(d + o_inl);
-        a.mask = reinterpret_cast<unsigned long long*>(d + o_mask);
+        a.frames = o_frames.at(d); a.obs = o_obs.at(d); a.obs_smp = o_obs_smp.at(d); a.smp_dt = o_smp_dt.at(d);
+        a.tri = o_tri.at(d); a.work_frame = o_work.at(d); a.camd = o_camd.at(d);
+        a.hyp_vel = o_hvel.at(d); a.frame_vel = o_fvel.at(d); a.hyp_inl = o_hinl.at(d); a.hyp_it = o_hit.at(d);
+        a.frame_best = o_best.at(d); a.inlier = o_inl.at(d); a.mask = o_mask.at(d);
         a.threshold = P.threshold; a.huber_delta = P.huber_delta; a.tau = t->cfg.tau;
         a.iterations = P.iterations; a.max_trials = t->cfg.max_trials; a.early_stop = t->cfg.early_stop;
         if (n_work) hipLaunchKernelGGL(k_vel_hyp, dim3((unsigned)n_work), dim3(VEL_WAVE), 0, s, a);
@@ -308,12 +297,9 @@ extern "C" int lba_track_vel_ransac(lba_tracker* t, lba_vel_frame* frames, int32
     } catch (const TrackerError& e) {
         return tracker_fail(t, e);
     }
-    const double* r_hvel = reinterpret_cast<const double*>(out.data() + (o_hvel - out0));
-    const double* r_fvel = reinterpret_cast<const double*>(out.data() + (o_fvel - out0));
-    const int* r_hinl = reinterpret_cast<const int*>(out.data() + (o_hinl - out0));
-    const int* r_hit = reinterpret_cast<const int*>(out.data() + (o_hit - out0));
-    const int* r_best = reinterpret_cast<const int*>(out.data() + (o_best - out0));
-    const int* r_inl = reinterpret_cast<const int*>(out.data() + (o_inl - out0));
+    const char* r = out.data();   // the arena from out0 on
+    const double *r_hvel = o_hvel.at(r, out0), *r_fvel = o_fvel.at(r, out0);
+    const int *r_hinl = o_hinl.at(r, out0), *r_hit = o_hit.at(r, out0), *r_best = o_best.at(r, out0), *r_inl = o_inl.at(r, out0);
     for (int f = 0; f < n_frames; ++f) {
         lba_vel_frame& F = frames[f];
         const VelFrame& V = vf[f];

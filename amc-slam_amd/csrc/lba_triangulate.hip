@@ -92,10 +92,7 @@ __global__ __launch_bounds__(TRI_WG) void k_triangulate(TriArgs A) {
 }  // namespace
 
 extern "C" int lba_triangulate_profile(lba_tracker* t, int32_t on, double* last_ms) {
-    if (!t) return LBA_E_ARG;
-    t->tri_timed = on != 0;
-    if (last_ms) *last_ms = t->tri_ms;
-    return LBA_OK;
+    return t ? t->tri_timer.profile(on, last_ms, 1) : LBA_E_ARG;
 }
 
 extern "C" int lba_triangulate(lba_tracker* t, lba_tri_pair* pairs, int32_t n_pairs, lba_tri_row* rows, int32_t n_rows,
@@ -127,29 +124,24 @@ extern "C" int lba_triangulate(lba_tracker* t, lba_tri_pair* pairs, int32_t n_pa
         return LBA_OK;
     }
     // ---- the arena: inputs (one upload), outputs (one download); its pinned host image has the same offsets
-    ArenaLayout lay;
-    const size_t o_chunks = lay.take(n_chunks * sizeof(TriChunk));
-    const size_t o_kfs = lay.take((size_t)n_kf * sizeof(lba_tri_kf));
-    const size_t o_cams = lay.take((size_t)n_cam_rows * sizeof(lba_tri_cam));
-    const size_t o_cam12 = lay.take(2 * n * sizeof(int));
-    const size_t o_field = lay.take(TRI_NF * n * sizeof(double));
-    const size_t out0 = lay.total;
-    const size_t o_status = lay.take(n * sizeof(int));
-    const size_t o_stereo = lay.take(n * sizeof(int));
-    const size_t o_X = lay.take(3 * n * sizeof(double));
-    const size_t out1 = lay.total;
-    if (n > 0x7fffffff || n_chunks > 0x7fffffff || lay.total > (size_t(1) << 31))
+    ArenaPlan plan;
+    const Sec<TriChunk> o_chunks = plan.in<TriChunk>(n_chunks);
+    const Sec<lba_tri_kf> o_kfs = plan.in<lba_tri_kf>((size_t)n_kf);
+    const Sec<lba_tri_cam> o_cams = plan.in<lba_tri_cam>((size_t)n_cam_rows);
+    const Sec<int> o_cam12 = plan.in<int>(2 * n);
+    const Sec<double> o_field = plan.in<double>(TRI_NF * n);
+    const Sec<int> o_status = plan.out<int>(n), o_stereo = plan.out<int>(n);
+    const Sec<double> o_X = plan.out<double>(3 * n);
+    if (n > 0x7fffffff || n_chunks > 0x7fffffff || plan.over_2gb())
         return tracker_fail(t, {LBA_E_LIMIT, "the batch's rows, keyframes and cameras exceed 2 GB"});
     char* h = nullptr;
     try {
-        TR_HIP(hipSetDevice(t->cfg.device));
-        grow_bytes(t->d_arena, t->arena_cap, lay.total, lay.total * 2);
-        grow_bytes(t->h_sim3, t->sim3_pin_cap, out1, out1 * 2, true);
-        h = t->h_sim3;
+        ArenaCall call{t, plan, t->tri_timer};
+        h = call.pin();
         // per pair: its rows packed in pair order (overlapping ranges get rows of their own), cut into chunks
-        TriChunk* ch = reinterpret_cast<TriChunk*>(h + o_chunks);
-        int* cam12 = reinterpret_cast<int*>(h + o_cam12);
-        double* fd = reinterpret_cast<double*>(h + o_field);
+        TriChunk* ch = o_chunks.at(h);
+        int* cam12 = o_cam12.at(h);
+        double* fd = o_field.at(h);
         size_t at = 0, c = 0;
         for (int p = 0; p < n_pairs; ++p) {
             const lba_tri_pair& P = pairs[p];
@@ -163,43 +155,28 @@ extern "C" int lba_triangulate(lba_tracker* t, lba_tri_pair* pairs, int32_t n_pa
                 for (int j = 0; j < TRI_NF; ++j) fd[(size_t)j * n + at] = v[j];
             }
         }
-        std::memcpy(h + o_kfs, kfs, (size_t)n_kf * sizeof(lba_tri_kf));
-        std::memcpy(h + o_cams, cams, (size_t)n_cam_rows * sizeof(lba_tri_cam));
-        char* d = t->d_arena;
-        hipStream_t s = t->stream;
-        if (t->tri_timed && !t->sim3_ev[0])
-            for (hipEvent_t& e : t->sim3_ev) TR_HIP(hipEventCreate(&e));
-        TR_HIP(hipMemcpyAsync(d, h, out0, hipMemcpyHostToDevice, s));
+        std::memcpy(o_kfs.at(h), kfs, (size_t)n_kf * sizeof(lba_tri_kf));
+        std::memcpy(o_cams.at(h), cams, (size_t)n_cam_rows * sizeof(lba_tri_cam));
+        char* d = call.place();
+        call.upload();
         TriArgs a;
-        a.chunks = reinterpret_cast<const TriChunk*>(d + o_chunks);
-        a.kfs = reinterpret_cast<const lba_tri_kf*>(d + o_kfs);
-        a.cams = reinterpret_cast<const lba_tri_cam*>(d + o_cams);
-        a.cam12 = reinterpret_cast<const int*>(d + o_cam12);
-        a.field = reinterpret_cast<const double*>(d + o_field);
-        a.status = reinterpret_cast<int*>(d + o_status);
-        a.stereo = reinterpret_cast<int*>(d + o_stereo);
-        a.X = reinterpret_cast<double*>(d + o_X);
+        a.chunks = o_chunks.at(d); a.kfs = o_kfs.at(d); a.cams = o_cams.at(d);
+        a.cam12 = o_cam12.at(d); a.field = o_field.at(d);
+        a.status = o_status.at(d); a.stereo = o_stereo.at(d); a.X = o_X.at(d);
         a.n = (int)n; a.n_cam = n_cam; a.far_points = far_points;
         a.ratio_factor = ratio_factor; a.th_far = th_far;
         const size_t lds = 8 * (2 * (size_t)n_cam * TRI_CAM_W + 2 * (size_t)TRI_KF_W);
-        if (t->tri_timed) TR_HIP(hipEventRecord(t->sim3_ev[0], s));
-        hipLaunchKernelGGL(k_triangulate, dim3((unsigned)n_chunks), dim3(TRI_WG), lds, s, a);
+        call.mark();
+        hipLaunchKernelGGL(k_triangulate, dim3((unsigned)n_chunks), dim3(TRI_WG), lds, t->stream, a);
         TR_HIP(hipGetLastError());
-        if (t->tri_timed) TR_HIP(hipEventRecord(t->sim3_ev[1], s));
-        TR_HIP(hipMemcpyAsync(h + out0, d + out0, out1 - out0, hipMemcpyDeviceToHost, s));
-        TR_HIP(hipStreamSynchronize(s));
-        if (t->tri_timed) {
-            float ms = -1.f;
-            TR_HIP(hipEventElapsedTime(&ms, t->sim3_ev[0], t->sim3_ev[1]));
-            t->tri_ms = ms;
-        }
+        call.mark();
+        call.finish();
     } catch (const TrackerError& e) {
         return tracker_fail(t, e);
     }
     // ---- scatter: status, stereo_point and X (under LBA_TRI_OK) into the rows; the counts from the statuses
-    const int* r_status = reinterpret_cast<const int*>(h + o_status);
-    const int* r_stereo = reinterpret_cast<const int*>(h + o_stereo);
-    const double* r_X = reinterpret_cast<const double*>(h + o_X);
+    const int *r_status = o_status.at(h), *r_stereo = o_stereo.at(h);
+    const double* r_X = o_X.at(h);
     // A row shared by two pairs carries the later pair's result alone (its X stays untouched unless THAT is
     // LBA_TRI_OK): the first pass leaves in `status` the packed index of the row's last visit, the second writes there.
     size_t at = 0;
