@@ -47,6 +47,21 @@ assert TRI_KF_DTYPE.itemsize == 120
 assert TRI_ROW_DTYPE.itemsize == 168
 assert TRI_PAIR_DTYPE.itemsize == 24
 
+# lba_match_epipolar (ORBmatcher::SearchForTriangulation); it shares TRI_KF_DTYPE / TRI_CAM_DTYPE
+EPI_FEAT_DTYPE = np.dtype([
+    ("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("u_right", "<f4"), ("scale", "<f4"), ("sigma2", "<f4"),
+    ("cam", "<i4"), ("has_point", "<i4"), ("desc", "<u4", (8,)),
+], align=True)
+EPI_KF_DTYPE = np.dtype([
+    ("feat0", "<i4"), ("n_feat", "<i4"), ("node0", "<i4"), ("n_node", "<i4"), ("nf0", "<i4"), ("pad", "<i4"),
+], align=True)
+EPI_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("out0", "<i4"), ("n_matches", "<i4")], align=True)
+EPI_ROW_DTYPE = np.dtype([("idx2", "<i4"), ("dist", "<i4"), ("status", "<i4"), ("pad", "<i4")], align=True)
+assert EPI_FEAT_DTYPE.itemsize == 64
+assert EPI_KF_DTYPE.itemsize == 24
+assert EPI_PAIR_DTYPE.itemsize == 16
+assert EPI_ROW_DTYPE.itemsize == 16
+
 # lba_match_project (ORBmatcher::SearchByProjection)
 MATCH_CAM_DTYPE = np.dtype([
     ("min_x", "<f4"), ("min_y", "<f4"), ("grid_w_inv", "<f4"), ("grid_h_inv", "<f4"), ("rounds", "<i4"),

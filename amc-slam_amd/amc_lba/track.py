@@ -132,6 +132,16 @@ class Tracker:
         from .triangulate import triangulate
         return triangulate(self, pairs, rows, kfs, cams, n_cam, params)
 
+    def match_epipolar(self, pairs, kfs, ekfs, cams, n_cam, feats, node_id, node_start, node_feat, params=None, out=None):
+        """ORBmatcher::SearchForTriangulation for a batch of (keyframe, neighbour) pairs, the matcher in front of
+        `triangulate` (lba_match_epipolar; amc_lba.epipolar has the dtypes, the caller's side and the generator)."""
+        from .epipolar import match_epipolar
+        return match_epipolar(self, pairs, kfs, ekfs, cams, n_cam, feats, node_id, node_start, node_feat, params, out)
+
+    def match_epipolar_kernel_ms(self, on=True):
+        """kernel_ms for lba_match_epipolar's two launches: (k_epi_tables, k_epi_match)"""
+        return kernel_ms(self, "lba_match_epipolar_profile", on, 2)
+
 
 def mc_ransac(tracker, frames, obs, samples, cams, min_match=30, outlier=None, params=None):
     """Tracking::MCRansac for a batch of frames with the caller's triples: the hypotheses on the GPU, then the

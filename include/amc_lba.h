@@ -568,7 +568,8 @@ int lba_sim3_ransac_profile(lba_tracker* t, int32_t on, double* last_ms);
 /* ---- local mapping: the triangulation of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:408-587, with
  * GeometricTools::Triangulate, src/GeometricTools.cc:47-66, and MultiKeyFrame::UnprojectStereo, src/KeyFrame.cc:829-846)
  * for a batch of (keyframe, neighbour) pairs, the step that makes the landmarks the next lba_set_problem receives.  One
- * row is one match of SearchForTriangulation (which stays on the CPU, like Fuse: greedy matching on map state); the
+ * row is one match of SearchForTriangulation (lba_match_epipolar below: in this reference it decides every keypoint
+ * on its own; Fuse stays on the CPU: greedy matching on map state); the
  * caller builds the rows (amc_lba.triangulate.tri_rows, :412-432, :498, :525, :565).  Per row, in fp64 on the
  * float-valued inputs widened, in the reference's order; the row gets the FIRST status that applies:
  *   rays      xn = ((u - cx) / fx, (v - cy) / fy, 1) of z1 / z2 with the row's camera (Pinhole::unprojectEig),
@@ -664,6 +665,101 @@ int lba_triangulate(lba_tracker* t, lba_tri_pair* pairs, int32_t n_pairs, lba_tr
 /* Measurement only: on != 0 makes lba_triangulate bracket its launch with two events on the tracker's stream;
  * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
 int lba_triangulate_profile(lba_tracker* t, int32_t on, double* last_ms);
+
+/* ---- local mapping: ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:947-1131, with Pinhole::project and
+ * Pinhole::epipolarConstrain, src/CameraModels/Pinhole.cpp:43-49, 107-129) for a batch of (keyframe, neighbour) pairs:
+ * the matcher whose vMatchedPairs are the rows of lba_triangulate.  It reuses lba_tri_kf / lba_tri_cam as they are
+ * (Tcw, Ow, fx, fy, cx, cy, cam0), so a caller builds those arrays once for both calls.
+ * The function is NOT greedy in this reference: vbMatched2 is declared (:979) and read (:1028) but never set, the map
+ * is read as it is on entry and nothing is written to it, so every keypoint of KF1 is decided on its own.
+ *   tables    per (pair, c1, c2): T12 = T1cw(c1) T2cw(c2)^-1, i.e. R12 = R1 R2^T, t12 = R1 Ow2 + t1;
+ *             F12 = ((K1^-T [t12]x) R12) K2^-1; the epipole ep = project2(R2 Ow1 + t2) = (fx x / z + cx, fy y / z + cy)
+ *             with no test on z.
+ *   walk      the nodes present in BOTH keyframes' feature vectors, in ascending node id (the merge with lower_bound).
+ *   idx1      every entry of KF1's list of a common node: has_point -> LBA_EPI_HAS_POINT; only_stereo and not stereo ->
+ *             LBA_EPI_NOT_STEREO.  Stereo is cam == n_cam - 1 && u_right >= 0 (`>= 0`: lba_match_project's rule is > 0).
+ *   idx2      every entry of KF2's list of that node IN LIST ORDER, from bestDist = th_low, bestIdx2 = -1: skipped when
+ *             it has a point, or under only_stereo is not stereo; dist = the 256-bit Hamming distance, skipped when
+ *             dist > th_low || dist > bestDist; when neither side is stereo, skipped when
+ *             (ep.x - x2)^2 + (ep.y - y2)^2 < 100 scale2 (KF2's scale of the candidate); unless `coarse` the epipolar
+ *             gate: (a, b, c) = (x1, y1, 1) F12, num = a x2 + b y2 + c, den = a^2 + b^2, den == 0 fails, else it passes
+ *             when num^2 / den < 3.84 unc with unc = sigma2 of the CANDIDATE (KF2).  A candidate that passes becomes
+ *             bestIdx2 with bestDist = dist.
+ *   result    bestIdx2 >= 0: LBA_EPI_OK; else LBA_EPI_NO_MATCH.  A keypoint of KF1 that is in no node, or whose node
+ *             KF2 does not hold: LBA_EPI_NO_NODE.  n_matches of a pair is the reference's nmatches; its rows with
+ *             LBA_EPI_OK in ascending idx1 are vMatchedPairs (amc_lba.epipolar.epi_matches).
+ *   check_orientation (CreateNewMapPoints builds ORBmatcher(0.6f, false): off): the histogram of :1071-1081 and
+ *             ComputeThreeMaxima on the host after the download; quirk (c).
+ * Precision: the tracker's convention, like lba_triangulate: fp64 on the float-valued inputs
+ * widened, in the reference's order; results are held against the restatement on SETTLED jobs only (every comparison
+ * further than 1e-9 relative from its gate).  NOT lba_match_project's float-bit convention: F12 goes through Eigen's
+ * float 3 x 3 inverse and three matrix products, whose operation order nobody can reproduce.
+ * Quirks of the reference that are kept:
+ *  (a) vbMatched2 is never set: several idx1 may get the same idx2; no state passes between keypoints.
+ *  (b) ties go to the LAST candidate in node-list order that passes the gates (`dist > bestDist` is the skip); a
+ *      candidate at distance exactly th_low can win; with bestDist shrinking a later candidate is tested only if
+ *      dist <= bestDist.
+ *  (c) the rotation pass removes the matches of the bins that ARE ind1, ind2 or ind3 (:1108 reads `i == ind1 || ...`,
+ *      the opposite of the projection search); n_matches loses one each; the row becomes LBA_EPI_ROT, idx2 is kept.
+ *  (d) unc is KF2's level sigma2 (kp1's sigmaLevel is passed and never read); 3.84 * unc is a double product there and
+ *      here.
+ *  (e) an epipole with z <= 0 falls where IEEE puts it: negative depth mirrors it, z == 0 gives +-inf or NaN, every
+ *      comparison with those is false, so nothing is skipped by the epipole test.
+ *  (f) den == 0 is false: two cameras with the same centre give t12 = 0, F12 = 0 and no match unless `coarse`.
+ *  (g) a node that only one keyframe holds contributes nothing.
+ * A batch is one upload, two launches (k_epi_tables: one thread per (pair, c1, c2); k_epi_match: one 64-lane wave per
+ * (pair, common node, chunk of 64 entries of KF1's list), the lane IS the idx1 and walks KF2's list in order) and one
+ * download; a keyframe's features and node lists are uploaded once however many pairs name it.  A pair's result does
+ * not depend on the batch and is bitwise reproducible.
+ * LBA_E_ARG: null tracker or arrays, a negative count, n_cam < 1, a range outside its array, a keyframe's cameras
+ * outside `cams`, node_id not strictly ascending within a keyframe, node_start not starting at 0, decreasing or past
+ * the end of node_feat, a node_feat entry outside [0, n_feat) or listed twice in one keyframe, a feature's cam outside
+ * [0, n_cam), th_low outside [0, 255], a pair's kf1 / kf2 outside [0, n_kf), two pairs whose `out` ranges overlap or a
+ * range that does not fit in [0, n_out).  LBA_E_LIMIT: n_cam > 64, or an arena above 2 GB.  A refused call writes
+ * nothing and sets lba_tracker_last_error.  n_pairs == 0, a keyframe without features or without nodes and a pair
+ * with kf1 == kf2 are valid. */
+#define LBA_EPI_OK         0
+#define LBA_EPI_HAS_POINT  1
+#define LBA_EPI_NOT_STEREO 2
+#define LBA_EPI_NO_NODE    3    /* the keypoint is in no node, or its node is not in KF2 */
+#define LBA_EPI_NO_MATCH   4    /* no candidate passed */
+#define LBA_EPI_ROT        5    /* accepted, then removed by quirk (c); idx2 is kept */
+typedef struct lba_epi_feat {      /* 64 bytes, one per keypoint of a keyframe, in the keyframe's global keypoint order */
+    float    x, y;                 /* mvKeysUn[idx].pt */
+    float    angle;                /* mvKeysUn[idx].angle (read with check_orientation only) */
+    float    u_right;              /* mvuRight[mmpGlobalToLocalID[idx]], anything < 0 where there is none */
+    float    scale;                /* mvScaleFactors[octave] */
+    float    sigma2;               /* mvLevelSigma2[octave] */
+    int32_t  cam;                  /* mmpKeyToCam[idx] */
+    int32_t  has_point;            /* GetMapPoint(idx) != NULL on entry */
+    uint32_t desc[8];
+} lba_epi_feat;
+typedef struct lba_epi_kf {        /* parallel to kfs[]: entry k describes lba_tri_kf k */
+    int32_t feat0, n_feat;         /* its rows of `feats` */
+    int32_t node0, n_node;         /* mFeatVec, node ids strictly ascending: its n_node rows of node_id and its n_node + 1
+                                      rows of node_start, both from row node0 (a packer gives a keyframe n_node + 1 rows) */
+    int32_t nf0, pad;              /* its entries of node_feat; node_start holds n_node + 1 offsets from nf0, the first 0 */
+} lba_epi_kf;
+typedef struct lba_epi_pair {
+    int32_t kf1, kf2;
+    int32_t out0;                  /* its n_feat(kf1) rows of `out` */
+    int32_t n_matches;             /* out */
+} lba_epi_pair;
+typedef struct lba_epi_row {       /* out, one per (pair, keypoint of KF1) */
+    int32_t idx2;                  /* bestIdx2 (keyframe-local keypoint index of KF2), or -1 */
+    int32_t dist;                  /* bestDist of the accepted candidate; th_low where idx2 == -1 */
+    int32_t status;                /* LBA_EPI_* */
+    int32_t pad;
+} lba_epi_row;
+typedef struct lba_epi_params { int32_t th_low, only_stereo, coarse, check_orientation; } lba_epi_params;  /* NULL: 50,0,0,0 */
+int lba_match_epipolar(lba_tracker* t, lba_epi_pair* pairs, int32_t n_pairs, lba_epi_row* out, int32_t n_out,
+                       const lba_tri_kf* kfs, const lba_epi_kf* ekfs, int32_t n_kf,
+                       const lba_tri_cam* cams, int32_t n_cam_rows, int32_t n_cam,
+                       const lba_epi_feat* feats, int32_t n_feats, const int32_t* node_id, const int32_t* node_start,
+                       int32_t n_node_rows, const int32_t* node_feat, int32_t n_node_feat, const lba_epi_params* prm);
+/* Measurement only: on != 0 makes lba_match_epipolar bracket its two launches with events on the tracker's stream;
+ * last_ms (may be NULL) receives the two kernel times (k_epi_tables, k_epi_match) of the last such call, or -1. */
+int lba_match_epipolar_profile(lba_tracker* t, int32_t on, double* last_ms);
 
 /* ---- tracking: ORBmatcher's two projection searches for a batch of frames: SearchByProjection(MultiFrame&,
  * const vector<MapPoint*>&, th, ...) (src/ORBmatcher.cc:43-217, Tracking::SearchLocalPoints) is LBA_MATCH_RATIO, and
