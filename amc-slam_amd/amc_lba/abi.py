@@ -62,6 +62,12 @@ assert EPI_KF_DTYPE.itemsize == 24
 assert EPI_PAIR_DTYPE.itemsize == 16
 assert EPI_ROW_DTYPE.itemsize == 16
 
+# lba_match_bow (ORBmatcher::SearchByBoW): the keyframe arrays are lba_match_epipolar's
+BOW_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("out0", "<i4"), ("n_matches", "<i4")], align=True)
+BOW_ROW_DTYPE = np.dtype([("idx2", "<i4"), ("dist", "<i4"), ("dist2", "<i4"), ("status", "<i4")], align=True)
+assert BOW_PAIR_DTYPE.itemsize == 16
+assert BOW_ROW_DTYPE.itemsize == 16
+
 # lba_match_project (ORBmatcher::SearchByProjection)
 MATCH_CAM_DTYPE = np.dtype([
     ("min_x", "<f4"), ("min_y", "<f4"), ("grid_w_inv", "<f4"), ("grid_h_inv", "<f4"), ("rounds", "<i4"),

@@ -142,6 +142,17 @@ class Tracker:
         """kernel_ms for lba_match_epipolar's two launches: (k_epi_tables, k_epi_match)"""
         return kernel_ms(self, "lba_match_epipolar_profile", on, 2)
 
+    def match_bow(self, pairs, ekfs, feats, node_id, node_start, node_feat, params=None, out=None):
+        """ORBmatcher::SearchByBoW for a batch of pairs, the matcher in front of `sim3_ransac` in loop closing and of
+        the pose optimisation in TrackReferenceKeyFrame (lba_match_bow; amc_lba.bow has the dtypes, the caller's side
+        and the generator).  The keyframe arrays are `match_epipolar`'s."""
+        from .bow import match_bow
+        return match_bow(self, pairs, ekfs, feats, node_id, node_start, node_feat, params, out)
+
+    def match_bow_kernel_ms(self, on=True):
+        """kernel_ms for lba_match_bow's launch (k_bow_match)"""
+        return kernel_ms(self, "lba_match_bow_profile", on)
+
 
 def mc_ransac(tracker, frames, obs, samples, cams, min_match=30, outlier=None, params=None):
     """Tracking::MCRansac for a batch of frames with the caller's triples: the hypotheses on the GPU, then the

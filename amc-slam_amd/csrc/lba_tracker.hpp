@@ -1,7 +1,7 @@
 // lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip),
 // lba_track_vel_ransac (lba_track_vel.hip), lba_sim3_ransac (lba_sim3_ransac.hip), lba_sim3_optimize (lba_sim3.hip),
-// lba_posegraph_* (lba_posegraph.hip), lba_triangulate (lba_triangulate.hip), lba_match_project (lba_match.hip) and
-// lba_match_epipolar (lba_epipolar.hip),
+// lba_posegraph_* (lba_posegraph.hip), lba_triangulate (lba_triangulate.hip), lba_match_project (lba_match.hip),
+// lba_match_epipolar (lba_epipolar.hip) and lba_match_bow (lba_bow.hip),
 // and what they have in common on the host: the error path, the call arena (its typed sections and its plan are in
 // lba_arena.hpp), the runner of a call on the pinned image (ArenaCall) and the camera records.
 // One stream, device buffers that grow and are reused across calls.  Calls on a tracker are serial.
@@ -42,14 +42,15 @@ struct lba_tracker {
     // every other entry point: one arena per call (inputs, outputs, work)
     char* d_arena = nullptr;
     size_t arena_cap = 0;                // in bytes
-    // lba_sim3_optimize / lba_sim3_ransac / lba_triangulate / lba_match_project / lba_match_epipolar: the pinned host
-    // image of the arena's inputs and outputs, and the events of whichever of them is timed
+    // lba_sim3_optimize / lba_sim3_ransac / lba_triangulate / lba_match_project / lba_match_epipolar / lba_match_bow:
+    // the pinned host image of the arena's inputs and outputs, and the events of whichever of them is timed
     char* h_arena = nullptr;
     size_t h_arena_cap = 0;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     CallTimer sim3_timer, s3r_timer, tri_timer;   // one bracket around the launch(es)
     CallTimer match_timer;                        // k_match_gather, k_match_resolve
     CallTimer epi_timer;                          // k_epi_tables, k_epi_match
+    CallTimer bow_timer;                          // k_bow_match
     double pg_ms[3] = {-1.0, -1.0, -1.0};   // lba_posegraph_profile: planning, upload, device of the last optimize
     std::string err;
     // every buffer and event is freed here and nowhere else (lba_tracker_destroy: device, synchronise, stream, delete)

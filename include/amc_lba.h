@@ -761,6 +761,73 @@ int lba_match_epipolar(lba_tracker* t, lba_epi_pair* pairs, int32_t n_pairs, lba
  * last_ms (may be NULL) receives the two kernel times (k_epi_tables, k_epi_match) of the last such call, or -1. */
 int lba_match_epipolar_profile(lba_tracker* t, int32_t on, double* last_ms);
 
+/* ---- loop closing and relocalisation: ORBmatcher::SearchByBoW for a batch of pairs, both overloads:
+ *   LBA_BOW_KF     (pKF1, pKF2, vpMatches12), src/ORBmatcher.cc:805-945: LoopClosing::DetectCommonRegionsFromBoW calls
+ *                  it once per (candidate, covisible keyframe) with mpCurrentKF as KF1 (LoopClosing.cc:485-496), the
+ *                  stage in front of lba_sim3_ransac and lba_sim3_optimize;
+ *   LBA_BOW_FRAME  (pKF, F, vpMapPointMatches), :227-421: Tracking::TrackReferenceKeyFrame.  Side 1 is the keyframe,
+ *                  side 2 the frame.
+ * `ekfs`, `feats`, `node_id`, `node_start` and `node_feat` are exactly lba_match_epipolar's arrays (a frame is one more
+ * lba_epi_kf entry); there are no keyframe poses and no cameras, the matcher has no geometry: of lba_epi_feat only
+ * desc, has_point and (with check_orientation) angle are read.  has_point means "has a map point that is not bad"
+ * (:844-848, :864-870); has_point of side 2 is ignored in LBA_BOW_FRAME.  `angle` is whatever the caller's overload
+ * reads: mvKeysUn[..].angle on both sides at :897, but F.mvKeys[bestIdxF].angle, the RAW keypoint, for the frame at
+ * :342.
+ *   walk      the nodes present in BOTH sides' feature vectors, in ascending node id (the merge with lower_bound).
+ *   idx1      every entry of side 1's list of a common node IN LIST ORDER: without has_point -> LBA_BOW_NO_POINT.
+ *   idx2      every entry of side 2's list of that node in list order, from bestDist1 = bestDist2 = 256, bestIdx2 = -1:
+ *             skipped when it is matched already (vbMatched2[idx2], or vpMapPointMatches[idx2] != NULL: set by an
+ *             EARLIER idx1 of this call) or, in LBA_BOW_KF, has no point; dist = the 256-bit Hamming distance;
+ *             dist < bestDist1: bestDist2 = bestDist1, bestDist1 = dist, bestIdx2 = idx2; else dist < bestDist2:
+ *             bestDist2 = dist.
+ *   accept    bestDist1 < th_low (LBA_BOW_KF) or bestDist1 <= th_low (LBA_BOW_FRAME), else LBA_BOW_NO_CAND; then
+ *             (float)bestDist1 < nn_ratio * (float)bestDist2 (one float product), else LBA_BOW_RATIO; accepted:
+ *             LBA_BOW_OK and idx2 is matched from here on.
+ *   rotation  with check_orientation, on the host after the download: the ORDINARY rule (:932-941, :408-417): the
+ *             matches of the bins that are NOT one of ComputeThreeMaxima's three are removed (LBA_BOW_ROT, idx2 kept).
+ *             This is the opposite of lba_match_epipolar's quirk (c).  A removed match stays matched for the scan: the
+ *             pass runs after the loops.
+ *   result    idx2, dist, dist2 of a row are bestIdx2, bestDist1, bestDist2 as the reference holds them after the inner
+ *             loop, for every status that ran it (OK, NO_CAND, RATIO, ROT); -1, 256, 256 for NO_POINT and NO_NODE.
+ *             n_matches of a pair is the reference's return value.  The output is indexed by the keypoint of side 1 in
+ *             both modes: vpMatches12[idx1] = the point of row.idx2 (LBA_BOW_KF); a LBA_BOW_FRAME caller scatters
+ *             vpMapPointMatches[row.idx2] = the point of idx1 (amc_lba.bow.frame_matches).  idx2 is unique among the
+ *             OK and ROT rows of a pair.
+ * The matched flag is indexed by idx2 and DBoW2 puts every feature into exactly one node (TemplatedVocabulary::transform
+ * calls addFeature once per feature), so no state crosses a node: every (pair, common node) is an independent, short
+ * sequential problem.  k_bow_match gives one 64-lane wave to each: idx1 serially, the node's candidates in parallel
+ * (lane l owns l, l + 64, ...; its matched flags are 32 bits of a register), the best and the second best by one
+ * wave-wide merge of the lanes' scans (lba_bow_math.hpp has the proof that a scan may be split).  The results are the reference's own,
+ * bit for bit; a pair's result does not depend on the batch.  One upload, one launch, one download; a keyframe's
+ * features and node lists go up once however many pairs name it.
+ * LBA_E_ARG: null tracker or arrays, a negative count, a range outside its array, node_id not strictly ascending
+ * within a keyframe, node_start not starting at 0, decreasing or past the end of node_feat, a node_feat entry outside
+ * [0, n_feat) or listed twice in one keyframe (what makes nodes independent), a pair's kf1 / kf2 outside [0, n_kf),
+ * two pairs whose `out` ranges overlap or a range that does not fit in [0, n_out), th_low outside [0, 255], nn_ratio
+ * not finite, an unknown mode.  LBA_E_LIMIT: a side-2 node list longer than LBA_BOW_MAX_NODE, or an arena above 2 GB.
+ * A refused call writes nothing and sets lba_tracker_last_error.  n_pairs == 0, a keyframe without features or without
+ * nodes and a pair with kf1 == kf2 are valid. */
+#define LBA_BOW_KF    0   /* :805  side 2 needs a point; accept bestDist1 <  th_low */
+#define LBA_BOW_FRAME 1   /* :227  side 2 = frame features, no point needed; accept bestDist1 <= th_low */
+#define LBA_BOW_OK       0
+#define LBA_BOW_NO_POINT 1    /* idx1 has no usable point */
+#define LBA_BOW_NO_NODE  2    /* the keypoint is in no node, or its node is not in side 2 */
+#define LBA_BOW_NO_CAND  3    /* the threshold failed; this includes an empty list */
+#define LBA_BOW_RATIO    4    /* the ratio test failed */
+#define LBA_BOW_ROT      5    /* accepted, then removed by the rotation pass; idx2 is kept and stays matched */
+#define LBA_BOW_MAX_NODE 2048 /* entries of one node's list on side 2 */
+typedef struct lba_bow_pair { int32_t kf1, kf2, out0, n_matches /* out */; } lba_bow_pair;
+typedef struct lba_bow_row  { int32_t idx2, dist, dist2, status; } lba_bow_row;   /* one per (pair, keypoint of side 1) */
+typedef struct lba_bow_params { int32_t mode, th_low; float nn_ratio; int32_t check_orientation; } lba_bow_params;
+/* prm NULL: LBA_BOW_KF, 50, 0.9f, 1 (LoopClosing's matcherBoW(0.9, true)) */
+int lba_match_bow(lba_tracker* t, lba_bow_pair* pairs, int32_t n_pairs, lba_bow_row* out, int32_t n_out,
+                  const lba_epi_kf* ekfs, int32_t n_kf, const lba_epi_feat* feats, int32_t n_feats,
+                  const int32_t* node_id, const int32_t* node_start, int32_t n_node_rows,
+                  const int32_t* node_feat, int32_t n_node_feat, const lba_bow_params* prm);
+/* Measurement only: on != 0 makes lba_match_bow bracket its launch with two events on the tracker's stream;
+ * last_ms (may be NULL) receives the kernel time of the last such call in milliseconds, or -1. */
+int lba_match_bow_profile(lba_tracker* t, int32_t on, double* last_ms);
+
 /* ---- tracking: ORBmatcher's two projection searches for a batch of frames: SearchByProjection(MultiFrame&,
  * const vector<MapPoint*>&, th, ...) (src/ORBmatcher.cc:43-217, Tracking::SearchLocalPoints) is LBA_MATCH_RATIO, and
  * SearchByProjection(MultiFrame& Current, const MultiFrame& Last, th, bMono) (:1439-1568, TrackWithMotionModel) is
