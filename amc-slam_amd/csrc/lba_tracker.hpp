@@ -1,7 +1,7 @@
 // lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip),
 // lba_track_vel_ransac (lba_track_vel.hip), lba_sim3_ransac (lba_sim3_ransac.hip), lba_sim3_optimize (lba_sim3.hip),
 // lba_posegraph_* (lba_posegraph.hip), lba_triangulate (lba_triangulate.hip), lba_match_project (lba_match.hip),
-// lba_match_epipolar (lba_epipolar.hip) and lba_match_bow (lba_bow.hip),
+// lba_match_epipolar (lba_epipolar.hip), lba_match_bow (lba_bow.hip) and lba_match_sim3_project (lba_sim3_project.hip),
 // and what they have in common on the host: the error path, the call arena (its typed sections and its plan are in
 // lba_arena.hpp), the runner of a call on the pinned image (ArenaCall) and the camera records.
 // One stream, device buffers that grow and are reused across calls.  Calls on a tracker are serial.
@@ -22,7 +22,7 @@ constexpr int TR_MAXS = 16;   // pose samples per frame: distinct camera time st
 // the event bracket of one entry point (lba_*_profile): switched by the caller, read back after a timed call
 struct CallTimer {
     bool on = false;
-    double ms[2] = {-1.0, -1.0};   // between consecutive marks of the last timed call; -1 before the first
+    double ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, -1.0};   // between consecutive marks of the last timed call; -1 before the first
     int profile(int32_t on_, double* last_ms, int n) {
         on = on_ != 0;
         for (int i = 0; last_ms && i < n; ++i) last_ms[i] = ms[i];
@@ -46,16 +46,20 @@ struct lba_tracker {
     // the pinned host image of the arena's inputs and outputs, and the events of whichever of them is timed
     char* h_arena = nullptr;
     size_t h_arena_cap = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev[7] = {};   // (lba_match_sim3_project marks seven times)
     CallTimer sim3_timer, s3r_timer, tri_timer;   // one bracket around the launch(es)
     CallTimer match_timer;                        // k_match_gather, k_match_resolve
     CallTimer epi_timer;                          // k_epi_tables, k_epi_match
     CallTimer bow_timer;                          // k_bow_match
+    CallTimer s3p_timer;                          // lba_match_sim3_project's six stretches
+    // lba_match_sim3_project: its candidate lists, sized by a readback between two launches (the arena cannot grow there)
+    char* d_cand = nullptr;
+    size_t cand_cap = 0;                 // in bytes
     double pg_ms[3] = {-1.0, -1.0, -1.0};   // lba_posegraph_profile: planning, upload, device of the last optimize
     std::string err;
     // every buffer and event is freed here and nowhere else (lba_tracker_destroy: device, synchronise, stream, delete)
     ~lba_tracker() {
-        void* bufs[] = {d_frames, d_obs, d_obs_smp, d_smp0, d_smp_obs0, d_smp_kf, d_smp_t, d_camd, d_chi2, d_arena};
+        void* bufs[] = {d_frames, d_obs, d_obs_smp, d_smp0, d_smp_obs0, d_smp_kf, d_smp_t, d_camd, d_chi2, d_arena, d_cand};
         for (void* b : bufs)
             if (b) (void)hipFree(b);
         if (h_arena) (void)hipHostFree(h_arena);

@@ -949,6 +949,128 @@ int lba_match_profile(lba_tracker* t, int32_t on, double* last_ms /* [2] */);
 /* The text of the last refusal or failure of a call on this tracker ("" before the first). */
 const char* lba_tracker_last_error(const lba_tracker* t);
 
+/* ---- loop closing: the Sim3 ORBmatcher::SearchByProjection, both overloads (src/ORBmatcher.cc:423-548 and :550-685;
+ * LoopClosing.cc:586, :608 and :800), for a batch of hypotheses against ONE keyframe.  The keyframe (its features, its
+ * 64 x 48 CSR grid as one search of lba_match_project has it, one lba_match_cam and one lba_s3p_cam per camera) is shared
+ * by the whole batch; every *search* is a hypothesis: its own Sbw and its own range of `points`.  A *job* is one
+ * (search, point, camera), in the reference's loop order (point-major, cameras inner): row `row0 + p * n_cam + c`.
+ *
+ * Per (search, camera), in fp64 on the float inputs widened (the tracker's convention): Tbw = (R(Sbw), t / s),
+ * Twb = Tbw^-1, Tcl = Tbw_kf * Tbw_prev^-1, Twl = Twb * Tcl, Twb_c = QueryPose(Twl, Twb, v_prev, v, stamp_prev, stamp,
+ * stamp_c), Tcw[c] = (Twb_c * Tbc[c])^-1, written as 12 doubles (R row-major, then t) and rounded ONCE to 12 floats.  The
+ * reference rounds Twb_c to float and finishes in SE3f; its float quaternion products are not reproduced (as for
+ * lba_match_project).  QueryPose does not depend on Qc, so none is passed.
+ * Per job, in FLOAT, in this operation order, without contraction, divide and square root correctly rounded:
+ *   p3Dc = ((r0 x + r1 y) + r2 z) + t per row; z < 0 -> BEHIND;
+ *   proj_form 0 (Pinhole::project, :480): u = fx * X / Z + cx; proj_form 1 (:610-615): invz = 1 / Z, u = fx * (X * invz) + cx;
+ *   IsInImage: u >= min_x && u < max_x && v >= min_y && v < max_y, else OUT_OF_IMAGE;
+ *   PO = p - ow[c], dist = sqrt((x^2 + y^2) + z^2); dist < min_dist || dist > max_dist -> DIST;
+ *   (PO.x n.x + PO.y n.y) + PO.z n.z < 0.5f * dist -> ANGLE;
+ *   PredictScale: ratio = max_distance / dist in float, level = ceil(log((double)ratio) / (double)log_scale_factor),
+ *   clamped to [0, n_levels - 1]; radius = (float)th * scale_factors[level];
+ *   GetFeaturesInArea's rectangle and window test, keypoint levels [level - 1, level], the Hamming distance, the best with
+ *   strict <, the first on a tie, 256 never wins; accepted when (float)best_dist <= (float)th_low * ratio_hamming; an
+ *   accepted job takes its feature for every later job of the search (vpMatched[bestIdx] = pMP).
+ * Quirks of the reference that are kept:
+ *  (a) PO and dist use GetCameraCenter(c) of the MAP pose (ow), the projection uses the Sim3-corrected pose (:489, :624).
+ *  (b) a point that matched in camera c goes on to camera c + 1 and may match again; n_matches counts both.
+ *  (c) spAlreadyFound is built once on entry: `skip` is the caller's isBad() || spAlreadyFound.count(pMP).
+ *  (d) z == 0 passes `z < 0.0`; the projection is +-inf or NaN, every IsInImage comparison fails: OUT_OF_IMAGE.
+ *  (e) Ow = Tbw^-1's translation is computed there and never read; it is not computed here.
+ *  (f) `0.5 * dist` is a double product there; halving is exact, so 0.5f * dist decides the same.
+ *  (g) with floor(th_low * ratio_hamming) >= 256 the reference indexes vpMatched[-1]: refused with LBA_E_ARG.
+ *  (h) dist == 0 or a ratio that is not finite makes (int)ceil(..) undefined there.  Here the quotient is clamped before
+ *      the conversion: NaN -> level 0, +inf -> n_levels - 1, -inf -> 0.
+ * Device (lba_sim3_project.hip): k_s3p_pose, k_s3p_project (one thread per job), k_s3p_compact (one workgroup per
+ * (search, camera): its live jobs in order and their list offsets), k_s3p_base, ONE readback of the per-(search, camera)
+ * totals that sizes the candidate lists, k_s3p_gather (one wave per live job), k_s3p_resolve (one workgroup per (search,
+ * camera): the sequential loop exactly, in rounds, as k_match_resolve).  One upload, one download; nothing waits on
+ * another workgroup.  A search's result does not depend on the batch or on its position.
+ * LBA_E_ARG: null tracker or arrays, a negative count, n_cam < 1, n_levels < 1, a malformed grid (as lba_match_project), a
+ * search's point range outside `points`, its taken row outside `taken`, its rows, feature entries or poses outside their
+ * arrays or beginning before the end of the search before, th < 0, th_low < 0, a ratio_hamming that is not finite or
+ * negative, quirk (g), a proj_form other than 0 or 1.  LBA_E_LIMIT: n_cam > 64, more than LBA_MATCH_MAX_FEAT features in
+ * one camera, arena and candidate lists above 2 GB.  A refused call writes nothing and sets lba_tracker_last_error.
+ * n_searches == 0, a search without points, a keyframe without features and has_prev == 0 (every row LBA_S3P_NO_PREV,
+ * n_matches 0, as the reference returns before it projects) are valid. */
+#define LBA_S3P_OK           0
+#define LBA_S3P_NO_CAND      1   /* no candidate in the window, or every one taken or at another level */
+#define LBA_S3P_TOO_FAR      2   /* bestDist > TH_LOW * ratioHamming */
+#define LBA_S3P_SKIPPED      3
+#define LBA_S3P_BEHIND       4
+#define LBA_S3P_OUT_OF_IMAGE 5
+#define LBA_S3P_DIST         6
+#define LBA_S3P_ANGLE        7
+#define LBA_S3P_NO_PREV      8
+#define LBA_S3P_MAX_CAM      64
+typedef struct lba_s3p_kf {        /* 136 bytes */
+    double  stamp, stamp_prev;     /* mTimeStamp of the keyframe and of mPrevKF */
+    float   q[4], t[3];            /* GetPose(): q as x, y, z, w */
+    float   q_prev[4], t_prev[3];  /* mPrevKF->GetPose() */
+    float   v[6], v_prev[6];       /* GetVelocity() of both */
+    float   log_scale_factor;      /* mfLogScaleFactor */
+    int32_t has_prev;              /* mPrevKF != NULL */
+    int32_t n_levels;              /* mnScaleLevels: entries of scale_factors */
+    int32_t n_cam;
+} lba_s3p_kf;
+typedef struct lba_s3p_cam {       /* 88 bytes */
+    double  stamp;                 /* mvTimeStamps[c] */
+    float   q_bc[4], t_bc[3];      /* mTbc[c] */
+    float   fx, fy, cx, cy;
+    float   min_x, max_x, min_y, max_y;   /* mvMinX[c] .. mvMaxY[c] */
+    float   ow[3];                 /* GetCameraCenter(c) of the map pose: quirk (a) */
+    int32_t pad[2];
+} lba_s3p_cam;
+typedef struct lba_s3p_point {     /* 80 bytes */
+    float    pos[3], normal[3];    /* GetWorldPos(), GetNormal() */
+    float    min_dist, max_dist;   /* GetMinDistanceInvariance(), GetMaxDistanceInvariance() (with 0.8 / 1.2) */
+    float    max_distance;         /* mfMaxDistance, raw: PredictScale reads it */
+    int32_t  skip;                 /* isBad() || spAlreadyFound.count(pMP) */
+    uint32_t desc[8];
+    int32_t  pad[2];
+} lba_s3p_point;
+typedef struct lba_s3p_search {    /* 64 bytes */
+    float   q[4], t[3], s;         /* Sbw */
+    int32_t point0, n_points;      /* its range of `points` (ranges may be shared) */
+    int32_t taken0;                /* its n_feats bytes of `taken` (vpMatched[idx] != NULL on entry), or -1: all free */
+    int32_t row0;                  /* its n_points * n_cam rows of `rows` */
+    int32_t featpt0;               /* its n_feats entries of `feat_point` */
+    int32_t pose0;                 /* its n_cam entries of `poses` */
+    int32_t n_matches;             /* out */
+    int32_t pad;
+} lba_s3p_search;
+typedef struct lba_s3p_row {       /* out, 32 bytes: one job */
+    int32_t status;                /* LBA_S3P_* */
+    int32_t feat;                  /* the feature won, or -1 */
+    int32_t best_dist;             /* 256: none */
+    int32_t level;                 /* nPredictedLevel, -1 for a job that failed a gate */
+    float   x, y, radius;          /* echoed; 0 where they were not reached */
+    int32_t pad;
+} lba_s3p_row;
+typedef struct lba_s3p_pose {      /* out, 152 bytes: one (search, camera) */
+    double  tcw_d[12];             /* Tcw[c] before rounding: R row-major, t */
+    float   tcw[12];               /* what the jobs use */
+    int32_t rounds;                /* rounds k_s3p_resolve needed */
+    int32_t pad;
+} lba_s3p_pose;
+typedef struct lba_s3p_params {
+    int32_t th, th_low;            /* th; TH_LOW (50) */
+    float   ratio_hamming;
+    int32_t proj_form;             /* 0: fx * X / Z + cx (:480); 1: fx * (X * (1 / Z)) + cx (:610-615) */
+} lba_s3p_params;
+/* feat_point[featpt0 + f]: the search-local index of the point feature f holds at the end (vpMatched), or -1. */
+int lba_match_sim3_project(lba_tracker* t, const lba_s3p_kf* kf, const lba_s3p_cam* kcams, const lba_match_cam* gcams,
+                           const float* scale_factors, const int32_t* cell_start, int32_t n_cell_start,
+                           const int32_t* cell_feat, int32_t n_cell_feat, const lba_match_feat* feats, int32_t n_feats,
+                           lba_s3p_search* searches, int32_t n_searches, const lba_s3p_point* points, int32_t n_points,
+                           const uint8_t* taken, int32_t n_taken, lba_s3p_row* rows, int32_t n_rows,
+                           int32_t* feat_point, int32_t n_feat_point, lba_s3p_pose* poses, int32_t n_poses,
+                           const lba_s3p_params* prm);
+/* Measurement only: on != 0 makes lba_match_sim3_project bracket its launches with events on the tracker's stream;
+ * last_ms (may be NULL) receives {k_s3p_pose, k_s3p_project, k_s3p_compact + k_s3p_base, the readback and the host's
+ * sizing, k_s3p_gather, k_s3p_resolve} of the last such call in milliseconds, or -1. */
+int lba_match_sim3_project_profile(lba_tracker* t, int32_t on, double* last_ms /* [6] */);
+
 /* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
  * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
  * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one
