@@ -90,6 +90,28 @@ assert MATCH_FEAT_DTYPE.itemsize == 64
 assert MATCH_JOB_DTYPE.itemsize == 96
 assert MATCH_SEARCH_DTYPE.itemsize == 40
 
+# lba_match_fuse (ORBmatcher::Fuse's search); the points are lba_match_sim3_project's (sim3_project.S3P_POINT_DTYPE)
+FUSE_CAM_DTYPE = np.dtype([
+    ("q_cw", "<f4", (4,)), ("t_cw", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+    ("min_x", "<f4"), ("max_x", "<f4"), ("min_y", "<f4"), ("max_y", "<f4"), ("ow", "<f4", (3,)),
+], align=True)
+FUSE_TARGET_DTYPE = np.dtype([
+    ("cam0", "<i4"), ("n_cam", "<i4"), ("feat0", "<i4"), ("n_feat", "<i4"), ("cell0", "<i4"), ("cf0", "<i4"),
+    ("bf", "<f4"), ("log_scale_factor", "<f4"), ("n_levels", "<i4"), ("sf0", "<i4"), ("sigma0", "<i4"), ("pad", "<i4"),
+], align=True)
+FUSE_SEARCH_DTYPE = np.dtype([
+    ("target", "<i4"), ("point0", "<i4"), ("n_points", "<i4"), ("row0", "<i4"), ("mode", "<i4"), ("th", "<f4"),
+    ("n_ok", "<i4"), ("pad", "<i4"),
+], align=True)
+FUSE_ROW_DTYPE = np.dtype([
+    ("status", "<i4"), ("feat", "<i4"), ("best_dist", "<i4"), ("level", "<i4"), ("x", "<f4"), ("y", "<f4"),
+    ("radius", "<f4"), ("n_cand", "<i4"),
+], align=True)
+assert FUSE_CAM_DTYPE.itemsize == 72
+assert FUSE_TARGET_DTYPE.itemsize == 48
+assert FUSE_SEARCH_DTYPE.itemsize == 32
+assert FUSE_ROW_DTYPE.itemsize == 32
+
 assert KF_DTYPE.itemsize == 128
 assert OBS_DTYPE.itemsize == 64
 assert PRIOR_DTYPE.itemsize == 8

@@ -1071,6 +1071,113 @@ int lba_match_sim3_project(lba_tracker* t, const lba_s3p_kf* kf, const lba_s3p_c
  * sizing, k_s3p_gather, k_s3p_resolve} of the last such call in milliseconds, or -1. */
 int lba_match_sim3_project_profile(lba_tracker* t, int32_t on, double* last_ms /* [6] */);
 
+/* ---- local mapping and loop closing: the SEARCH of ORBmatcher::Fuse, both overloads (src/ORBmatcher.cc:1133-1316 and
+ * :1318-1437; LocalMapping::SearchInNeighbors, LoopClosing::SearchAndFuse), for a batch of searches.  Which feature a
+ * (point, camera) picks, and at what distance, depends on the point's position, normal, distance range and descriptor
+ * and on the keyframe's features, grid and camera poses, and on nothing else: neither overload keeps a vbMatched or
+ * taken flag.  The map enters only in the skip in front (isBad, IsInKFCamera, spAlreadyFound) and in the decision
+ * behind (GetMapPoint(bestIdx), Observations(), Replace / AddObservation / vpReplacePoint); both stay with the caller
+ * (amc_lba.fuse.fuse_walk is that tail).  So this call writes one row per job and edits nothing.
+ *
+ * A *target* is a keyframe: its cameras (one lba_fuse_cam and one lba_match_cam each, at cam0 + c), its features
+ * (numbered from 0 within the target, as cell_feat and `feat` number them), its own 64 x 48 CSR grid per camera as a
+ * search of lba_match_project has it (cell0: its n_cam * 64 * 48 + 1 entries of cell_start, the first 0; cf0: its
+ * entries of cell_feat), its pyramid (sf0 / sigma0: n_levels entries of scale_factors / inv_level_sigma2 each).
+ * A *search* is one target, one range of `points` (ranges may be shared), a mode and th.  A *job* is one (search,
+ * point, camera), in the reference's loop order: row `row0 + p * n_cam + c`.
+ *
+ * Per job, every float expression in FLOAT, in this order, without contraction, divide and square root correctly
+ * rounded:
+ *   p3Dc = vTcw[c] * p3Dw as Sophus' SO3::operator* (so3.hpp:358-367) on the float quaternion as stored:
+ *     uv = qv x p (Eigen's order: a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x); uv += uv;
+ *     ((p + w * uv) + qv x uv) per component, then + t.  (Not the matrix form of lba_match_sim3_project.)
+ *   z < 0 -> BEHIND; u = fx * X / Z + cx, v likewise (Pinhole::project); IsInImage (u >= min_x && u < max_x && ..)
+ *   else OUT_OF_IMAGE; PO = p - ow[c], dist = sqrt((x^2 + y^2) + z^2); dist < min_dist || dist > max_dist -> DIST;
+ *   (PO.x n.x + PO.y n.y) + PO.z n.z < 0.5f * dist -> ANGLE; PredictScale as lba_match_sim3_project's (clamped, its
+ *   quirk (h)); radius = th * scale_factors[level]; GetFeaturesInArea's rectangle and window test; the candidates in
+ *   ITS order (ix, then iy, then the cell's list); keypoint levels [level - 1, level].
+ *   LBA_FUSE_KF (overload 1): every camera; ur = u - bf * (1.0f / Z); in the LAST camera a feature with u_right >= 0
+ *     has e2 = (ex^2 + ey^2) + er^2 and is dropped when (double)(e2 * inv_level_sigma2[kpLevel]) > 7.8; every other
+ *     feature e2 = ex^2 + ey^2 against 5.99 (the float product against the double literal, :1264 / :1275).  The best
+ *     starts at 256 with strict <: a distance of 256 never wins and leaves feat -1.
+ *   LBA_FUSE_SIM3 (overload 2): cameras 0 .. n_cam - 2; the last camera's rows are LBA_FUSE_NO_CAMERA.  No error gate.
+ *     The best starts at INT_MAX: a distance of 256 can win (feat names it) and is then rejected.  ow[c] is the
+ *     caller's vTcw[c].inverse().translation().
+ *   accepted (LBA_FUSE_OK) when best_dist <= th_low, else LBA_FUSE_TOO_FAR; LBA_FUSE_NO_CAND when the window is empty
+ *   or no candidate passed the level and error gates (best_dist 256, feat -1).
+ * ONLY LBA_FUSE_OK and LBA_FUSE_TOO_FAR rows depend on the point's descriptor: every other status is decided before a
+ * descriptor is read, and n_cand, level, x, y and radius never depend on it.  The caller's ordered walk rests on this:
+ * a point whose descriptor an earlier Replace changed needs its OK / TOO_FAR rows redone and no others.
+ * The call does NOT apply IsInKFCamera: every camera of every point whose `skip` is 0 is computed.  A point that
+ * loses a Replace has its observations cleared, and the reference then searches cameras it would have skipped.
+ * Quirks of the reference that are kept: (a) the last camera is skipped in overload 2; (b) Scw is unused there (:1328
+ * is commented out); (c) the stereo test is u_right >= 0, zero counts; (d) z == 0 passes `z < 0` and ends
+ * OUT_OF_IMAGE; (e) bRight is unused; (f) a point fused in camera c goes on to camera c + 1.
+ * Device (lba_fuse.hip): ONE launch, k_fuse; a wave takes 64 consecutive jobs, lane = job for the projection and the
+ * gates, then walks its live jobs one by one with all 64 lanes striding the window's spans.  No atomics, no LDS, no
+ * wait on another workgroup; one upload, one download.  A row does not depend on the batch or on its position.
+ * LBA_E_ARG: null tracker or arrays, a negative count, a target's n_cam < 1 or n_levels < 1, a target's camera,
+ * feature, grid or pyramid range outside its array, a malformed grid (as lba_match_project), a search's target or
+ * points outside their arrays, its rows outside `rows` or beginning before the end of the search before, a mode other
+ * than the two, th negative or not finite, th_low negative.  LBA_E_LIMIT: n_cam > 64, more than LBA_MATCH_MAX_FEAT
+ * features in one camera, an arena above 2 GB.  A refused call writes nothing and sets lba_tracker_last_error.
+ * n_searches == 0, a search without points, a target without features and n_cam == 1 in LBA_FUSE_SIM3 (every row
+ * LBA_FUSE_NO_CAMERA) are valid. */
+#define LBA_FUSE_KF   0
+#define LBA_FUSE_SIM3 1
+#define LBA_FUSE_OK           0
+#define LBA_FUSE_NO_CAND      1
+#define LBA_FUSE_TOO_FAR      2
+#define LBA_FUSE_SKIPPED      3
+#define LBA_FUSE_BEHIND       4
+#define LBA_FUSE_OUT_OF_IMAGE 5
+#define LBA_FUSE_DIST         6
+#define LBA_FUSE_ANGLE        7
+#define LBA_FUSE_NO_CAMERA    8
+#define LBA_FUSE_MAX_CAM      64
+typedef struct lba_fuse_cam {      /* 72 bytes: one per (target, camera) */
+    float   q_cw[4], t_cw[3];      /* mTcw[c]: the float unit quaternion as stored (x, y, z, w) and the translation */
+    float   fx, fy, cx, cy;
+    float   min_x, max_x, min_y, max_y;   /* mvMinX[c] .. mvMaxY[c] */
+    float   ow[3];                 /* KF: GetCameraCenter(c); SIM3: vTcw[c].inverse().translation() */
+} lba_fuse_cam;
+typedef struct lba_fuse_target {   /* 48 bytes */
+    int32_t cam0, n_cam;           /* its rows of `fcams` and `gcams` */
+    int32_t feat0, n_feat;         /* its rows of `feats` */
+    int32_t cell0, cf0;            /* its entries of `cell_start` and `cell_feat` */
+    float   bf;                    /* mbf */
+    float   log_scale_factor;      /* mfLogScaleFactor */
+    int32_t n_levels;              /* mnScaleLevels */
+    int32_t sf0, sigma0;           /* its n_levels entries of `scale_factors` and of `inv_level_sigma2` */
+    int32_t pad;
+} lba_fuse_target;
+typedef struct lba_fuse_search {   /* 32 bytes */
+    int32_t target;
+    int32_t point0, n_points;      /* its range of `points` */
+    int32_t row0;                  /* its n_points * n_cam rows of `rows` */
+    int32_t mode;                  /* LBA_FUSE_KF / LBA_FUSE_SIM3 */
+    float   th;
+    int32_t n_ok;                  /* out: its LBA_FUSE_OK rows */
+    int32_t pad;
+} lba_fuse_search;
+typedef struct lba_fuse_row {      /* out, 32 bytes: one job */
+    int32_t status;                /* LBA_FUSE_* */
+    int32_t feat;                  /* bestIdx, the target's keypoint index, or -1 */
+    int32_t best_dist;             /* 256: none */
+    int32_t level;                 /* nPredictedLevel, -1 for a job that failed a gate */
+    float   x, y, radius;          /* uv and the radius; 0 where they were not reached */
+    int32_t n_cand;                /* candidates that passed the window, level and error gates */
+} lba_fuse_row;
+int lba_match_fuse(lba_tracker* t, const lba_fuse_target* targets, int32_t n_targets, const lba_fuse_cam* fcams,
+                   const lba_match_cam* gcams, int32_t n_cams, const float* scale_factors, int32_t n_scale_factors,
+                   const float* inv_level_sigma2, int32_t n_inv_level_sigma2, const int32_t* cell_start,
+                   int32_t n_cell_start, const int32_t* cell_feat, int32_t n_cell_feat, const lba_match_feat* feats,
+                   int32_t n_feats, lba_fuse_search* searches, int32_t n_searches, const lba_s3p_point* points,
+                   int32_t n_points, lba_fuse_row* rows, int32_t n_rows, int32_t th_low);
+/* Measurement only: on != 0 makes lba_match_fuse bracket its launch with events on the tracker's stream; last_ms (may
+ * be NULL) receives {k_fuse} of the last such call in milliseconds, or -1. */
+int lba_match_fuse_profile(lba_tracker* t, int32_t on, double* last_ms /* [1] */);
+
 /* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
  * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
  * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one
