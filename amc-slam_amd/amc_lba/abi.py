@@ -112,6 +112,17 @@ assert FUSE_TARGET_DTYPE.itemsize == 48
 assert FUSE_SEARCH_DTYPE.itemsize == 32
 assert FUSE_ROW_DTYPE.itemsize == 32
 
+# lba_mappoint_refresh (MapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors); the keyframe arrays are
+# lba_match_epipolar's
+MP_OBS_DTYPE = np.dtype([("kf", "<i4"), ("feat", "<i4")], align=True)
+MP_POINT_DTYPE = np.dtype([
+    ("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"),
+    ("desc", "<u4", (8,)), ("ref_kf", "<i4"), ("obs0", "<i4"), ("n_obs", "<i4"), ("bad", "<i4"), ("ops", "<i4"),
+    ("n", "<i4"), ("best_obs", "<i4"), ("best_median", "<i4"), ("status", "<i4"), ("pad", "<i4", (3,)),
+], align=True)
+assert MP_OBS_DTYPE.itemsize == 8
+assert MP_POINT_DTYPE.itemsize == 112
+
 assert KF_DTYPE.itemsize == 128
 assert OBS_DTYPE.itemsize == 64
 assert PRIOR_DTYPE.itemsize == 8

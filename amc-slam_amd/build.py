@@ -17,8 +17,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libamc_lba.so")
-SOURCES = ["lba_kernels.hip", "lba_host.hip", "lba_track.hip", "lba_track_vel.hip", "lba_sim3.hip", "lba_sim3_ransac.hip", "lba_posegraph.hip", "lba_triangulate.hip", "lba_match.hip", "lba_epipolar.hip", "lba_bow.hip", "lba_sim3_project.hip", "lba_fuse.hip", "lba_debug.hip"]
-HEADERS = ["lba_arena.hpp", "lba_device.hpp", "lba_lm.hpp", "lba_math.hpp", "lba_pg_math.hpp", "lba_plan.hpp", "lba_s3r_math.hpp", "lba_setup.hpp", "lba_tracker.hpp", "lba_tri_math.hpp", "lba_match_math.hpp", "lba_epi_math.hpp", "lba_bow_math.hpp", "lba_s3p_math.hpp", "lba_fuse_math.hpp", os.path.join("..", "..", "include", "amc_lba.h")]
+SOURCES = ["lba_kernels.hip", "lba_host.hip", "lba_track.hip", "lba_track_vel.hip", "lba_sim3.hip", "lba_sim3_ransac.hip", "lba_posegraph.hip", "lba_triangulate.hip", "lba_match.hip", "lba_epipolar.hip", "lba_bow.hip", "lba_sim3_project.hip", "lba_fuse.hip", "lba_mappoint.hip", "lba_debug.hip"]
+HEADERS = ["lba_arena.hpp", "lba_device.hpp", "lba_lm.hpp", "lba_math.hpp", "lba_pg_math.hpp", "lba_plan.hpp", "lba_s3r_math.hpp", "lba_setup.hpp", "lba_tracker.hpp", "lba_tri_math.hpp", "lba_match_math.hpp", "lba_epi_math.hpp", "lba_bow_math.hpp", "lba_s3p_math.hpp", "lba_fuse_math.hpp", "lba_mp_math.hpp", os.path.join("..", "..", "include", "amc_lba.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall"]
 HOST = os.path.join(HERE, "host")

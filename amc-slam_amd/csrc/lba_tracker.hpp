@@ -1,8 +1,8 @@
 // lba_tracker.hpp — the tracking handle shared by its entry points: lba_track (lba_track.hip),
 // lba_track_vel_ransac (lba_track_vel.hip), lba_sim3_ransac (lba_sim3_ransac.hip), lba_sim3_optimize (lba_sim3.hip),
 // lba_posegraph_* (lba_posegraph.hip), lba_triangulate (lba_triangulate.hip), lba_match_project (lba_match.hip),
-// lba_match_epipolar (lba_epipolar.hip), lba_match_bow (lba_bow.hip), lba_match_sim3_project (lba_sim3_project.hip)
-// and lba_match_fuse (lba_fuse.hip), and what they have in common on the host: the error path, the call arena (its typed sections and its plan are in
+// lba_match_epipolar (lba_epipolar.hip), lba_match_bow (lba_bow.hip), lba_match_sim3_project (lba_sim3_project.hip),
+// lba_match_fuse (lba_fuse.hip) and lba_mappoint_refresh (lba_mappoint.hip), and what they have in common on the host: the error path, the call arena (its typed sections and its plan are in
 // lba_arena.hpp), the runner of a call on the pinned image (ArenaCall) and the camera records.
 // One stream, device buffers that grow and are reused across calls.  Calls on a tracker are serial.
 #pragma once
@@ -53,6 +53,7 @@ struct lba_tracker {
     CallTimer bow_timer;                          // k_bow_match
     CallTimer s3p_timer;                          // lba_match_sim3_project's six stretches
     CallTimer fuse_timer;                         // k_fuse
+    CallTimer mp_timer;                           // k_mp_geom, k_mp_desc_wave, k_mp_desc_block
     // lba_match_sim3_project: its candidate lists, sized by a readback between two launches (the arena cannot grow there)
     char* d_cand = nullptr;
     size_t cand_cap = 0;                 // in bytes

@@ -1178,6 +1178,89 @@ int lba_match_fuse(lba_tracker* t, const lba_fuse_target* targets, int32_t n_tar
  * be NULL) receives {k_fuse} of the last such call in milliseconds, or -1. */
 int lba_match_fuse_profile(lba_tracker* t, int32_t on, double* last_ms /* [1] */);
 
+/* ---- local mapping: MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:611-700) and
+ * MapPoint::ComputeDistinctiveDescriptors (:498-578) for a batch of map points: what LocalMapping::ProcessNewKeyFrame
+ * (:249-250), SearchInNeighbors (:687-688) and the tails of LocalGPBA / BundleAdjustment (Optimizer.cc:1416, :359) run
+ * point by point.  They fill the fields the projection matchers gate on: lba_s3p_point's normal, min_dist, max_dist,
+ * max_distance and desc.  A point's refresh reads its own position, observation list and reference keyframe, the
+ * keyframes' features and camera centres, and nothing else: no state passes from point to point, so a batch is the
+ * sequence exactly.
+ *
+ * The keyframe side is lba_match_epipolar's arrays as they are (a caller builds them once for match_epipolar,
+ * triangulate and this call): lba_tri_kf gives cam0; lba_tri_cam gives Ow, GetCameraCenter(c) widened to double, which
+ * is narrowed back to float here (exact for the map's values, which are floats; any other double is rounded to
+ * nearest); lba_epi_kf gives feat0 / n_feat; lba_epi_feat gives cam, scale (mvScaleFactors[octave]) and desc, in the
+ * keyframe's global keypoint order: the index :674 uses and, through mmpGlobalToLocalID, :534.  Nothing else of the
+ * four is read.  kf_bad[k] != 0: keyframe k isBad(); NULL: none is.
+ * obs: one entry per (keyframe, camera) observation: `feat` is the keyframe-local keypoint index, the camera is that
+ * feature's `cam`.  A point lists its observations IN THE REFERENCE'S ITERATION ORDER: mObservations' order, cameras
+ * ascending within a keyframe.  The float sum of the normal depends on that order and the device keeps it.
+ *
+ * Per point, ops bit 0 (normal and depth) and bit 1 (descriptor) select either function or both; neither reads what
+ * the other writes.
+ *   early     bad -> LBA_MP_BAD; n_obs == 0 -> LBA_MP_EMPTY; neither writes normal, min_distance, max_distance or desc.
+ *   desc      the candidates are the observations whose keyframe is NOT bad, in list order (:521); N their count.
+ *             N == 0: desc untouched, best_obs = best_median = -1.  Else the N x N matrix of 256-bit Hamming
+ *             distances; per row the element at sorted position int(0.5 * (N - 1)): the LOWER median, the row's own 0
+ *             included; the FIRST row with the strictly smallest median wins (:559-572).  desc = its descriptor,
+ *             best_obs = its position in the point's list, best_median = its median.  All integers: exact.
+ *   normal    over ALL observations in list order, bad keyframes included (:632-659), in FLOAT without contraction,
+ *             divide and square root correctly rounded: d = pos - Ow; r = sqrtf((dx dx + dy dy) + dz dz);
+ *             normal = normal + d / r (a true division per component); n++; at the end normal / (float)n.
+ *   depth     maxDist = FLT_MIN, minDist = FLT_MAX; over the observations with kf == ref_kf in list order:
+ *             maxDist = max(maxDist, r * scale), minDist = min(minDist, r * scale / scale_top) left to right, with
+ *             std::max / std::min's comparisons (a NaN never replaces).  max_distance = maxDist, min_distance = minDist
+ *             (the raw mfMaxDistance / mfMinDistance: the 1.2 / 0.8 of Get*DistanceInvariance are the caller's,
+ *             amc_lba.mappoint.points_to_s3p).
+ * Quirks of the reference that are kept: (a) the normal counts observations in bad keyframes, the descriptor skips
+ * them; (b) the lower median, ties to the first row; (c) a position on a camera centre gives 0 / 0: a NaN normal;
+ * (d) ref_kf == -1 (mpRefKF not among the observations) indexes an empty vector there, undefined behaviour; HERE it is
+ * defined as the host adapter defines it: no camera, FLT_MIN / FLT_MAX stored, the normal still computed.
+ * Device (lba_mappoint.hip): one upload, up to three launches, one download.  k_mp_geom: one lane per point walks
+ * its list in order.  The host sorts the descriptor points by N: k_mp_desc_wave (N <= 64) one wave per point, lane i
+ * holds candidate i, candidate j is broadcast; k_mp_desc_block (65 .. 1024) one 256-thread workgroup per point, the
+ * descriptors in LDS.  Both find a row's median by bisection on the value (9 steps over 0..256).  No atomics, no wait
+ * on another workgroup.  A point's result does not depend on the batch or on its position, and is bitwise
+ * reproducible.
+ * LBA_E_ARG: null tracker, arrays or params, a negative count, n_cam < 1, a keyframe's cameras or features outside
+ * their arrays, a feature's cam outside [0, n_cam), an observation's kf outside [0, n_kf) or feat outside its
+ * keyframe, a point's range outside `obs`, ref_kf outside [-1, n_kf), ops outside 1..3, a scale_top that is NaN.
+ * LBA_E_LIMIT: n_cam > 64, more than LBA_MATCH_MAX_FEAT features in one camera of a keyframe, a point with more than
+ * LBA_MP_MAX_OBS observations (the reference's float Distances[N][N] overruns an 8 MB stack near N = 1448), an arena
+ * above 2 GB.  A refused call writes nothing and sets lba_tracker_last_error.  n_points == 0 is valid; point ranges
+ * may overlap or be shared; `obs` is not written. */
+#define LBA_MP_OK      0
+#define LBA_MP_BAD     1
+#define LBA_MP_EMPTY   2
+#define LBA_MP_NORMAL  1           /* ops bit 0: UpdateNormalAndDepth */
+#define LBA_MP_DESC    2           /* ops bit 1: ComputeDistinctiveDescriptors */
+#define LBA_MP_MAX_OBS 1024
+typedef struct lba_mp_obs { int32_t kf, feat; } lba_mp_obs;
+typedef struct lba_mp_point {      /* 112 bytes */
+    float    pos[3];               /* mWorldPos */
+    float    normal[3];            /* in / out: mNormalVector */
+    float    min_distance, max_distance;   /* in / out: mfMinDistance, mfMaxDistance (raw) */
+    uint32_t desc[8];              /* in / out: mDescriptor */
+    int32_t  ref_kf;               /* mpRefKF's index in kfs, or -1: quirk (d) */
+    int32_t  obs0, n_obs;          /* its range of `obs` */
+    int32_t  bad;                  /* isBad() */
+    int32_t  ops;                  /* LBA_MP_NORMAL | LBA_MP_DESC */
+    int32_t  n;                    /* out: the observation count of :656; 0 where the normal was not computed */
+    int32_t  best_obs;             /* out: position in the point's list of the chosen descriptor, or -1 */
+    int32_t  best_median;          /* out: its median, or -1 */
+    int32_t  status;               /* out: LBA_MP_* */
+    int32_t  pad[3];
+} lba_mp_point;
+typedef struct lba_mp_params { float scale_top; } lba_mp_params;   /* mvScaleFactors[mnScaleLevels - 1] */
+int lba_mappoint_refresh(lba_tracker* t, lba_mp_point* points, int32_t n_points, const lba_mp_obs* obs, int32_t n_obs,
+                         const lba_tri_kf* kfs, const lba_epi_kf* ekfs, int32_t n_kf, const lba_tri_cam* cams,
+                         int32_t n_cam_rows, int32_t n_cam, const lba_epi_feat* feats, int32_t n_feats,
+                         const int32_t* kf_bad /* may be NULL */, const lba_mp_params* prm);
+/* Measurement only: on != 0 makes lba_mappoint_refresh bracket its launches with events on the tracker's stream;
+ * last_ms (may be NULL) receives {k_mp_geom, k_mp_desc_wave, k_mp_desc_block} of the last such call in milliseconds
+ * (about 0 for a kernel that was not launched), or -1. */
+int lba_mappoint_refresh_profile(lba_tracker* t, int32_t on, double* last_ms /* [3] */);
+
 /* ---- loop closing: the optimisation of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1434-1717, called from
  * LoopClosing::CorrectLoop), a Sim3 pose graph.  One g2o::VertexSim3Expmap per vertex (types_seven_dof_expmap.h:48-94:
  * estimate Siw, S <- Sim3(update) S, tangent [omega; upsilon; sigma], update[6] = 0 under fix_scale) and one
