@@ -42,6 +42,26 @@ int plan_probe(int NP, int NPk, int npairs, const int* pairs, int max_levels, in
     return pl.ntile();
 }
 
+// plan_probe at another leaf size and, with diagonal == 0, without the diagonal in lower[P]: the pose graph
+// (lba_posegraph.hip's pg_plan) calls make_plan with leaf 2 and lists only the panels below P that couple it.
+int plan_probe_leaf(int NP, int NPk, int npairs, const int* pairs, int max_levels, int tail_search, int method, int leaf,
+                    int diagonal, int* info, int* ppos, int* uord, int* rowptr, int* cols, int cap) {
+    auto lower = lower_of(NP, npairs, pairs);
+    if (!diagonal)
+        for (int P = 0; P < NP; ++P) lower[P].erase(std::remove(lower[P].begin(), lower[P].end(), P), lower[P].end());
+    const lba_plan::Plan pl = lba_plan::make_plan(NP, NPk, lower, max_levels, tail_search != 0, leaf, method);
+    info[0] = pl.chain;
+    info[1] = pl.tail;
+    info[2] = pl.levels;
+    info[3] = pl.ntile();
+    if (pl.ntile() > cap) return -1;
+    std::memcpy(ppos, pl.ppos.data(), sizeof(int) * NP);
+    std::memcpy(uord, pl.uord.data(), sizeof(int) * NP);
+    std::memcpy(rowptr, pl.rowptr.data(), sizeof(int) * (NP + 1));
+    std::memcpy(cols, pl.cols.data(), sizeof(int) * pl.ntile());
+    return pl.ntile();
+}
+
 // The distributed factorisation's split (lba_plan::split_subtrees) of the plan make_plan makes (the arguments
 // lba_set_problem / lba_partition_assign pass: 64 levels, tail search on, both methods): own[NP] the rank of
 // each factorisation position's subtree (-1 the top), parent[NP] its elimination-tree parent (-1 a root).

@@ -228,6 +228,51 @@ def test_flow_tasks_split(plan_harness, name, me):
     assert sorted(fac) == sorted(want)
 
 
+def plan_leaf(h, NP, pairs, leaf, diagonal, method=0):
+    """plan() through plan_probe_leaf: make_plan at another leaf size, with or without the diagonal in lower[P]."""
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    info = np.zeros(4, np.int32)
+    ppos, uord = np.zeros(NP, np.int32), np.zeros(NP, np.int32)
+    rowptr = np.zeros(NP + 1, np.int32)
+    cap = NP * NP
+    cols = np.zeros(cap, np.int32)
+    nt = h.plan_probe_leaf(NP, NP, len(pr), _p(pr), 64, 1, method, leaf, int(diagonal), _p(info), _p(ppos), _p(uord),
+                           _p(rowptr), _p(cols), cap)
+    assert nt == info[3] >= NP
+    return dict(chain=int(info[0]), tail=int(info[1]), levels=int(info[2]), ntile=int(nt), ppos=ppos, uord=uord,
+                rowptr=rowptr, cols=cols[:nt])
+
+
+def _posegraph_topology_cases():
+    import posegraph_topology_cases as tc
+    return tc.SINGLE_COMPONENT_CASES + tc.COMPONENT_CASES
+
+
+@pytest.mark.parametrize("name", _posegraph_topology_cases())
+def test_posegraph_settings(plan_harness, name):
+    """make_plan as the pose graph calls it (lba_posegraph.hip's pg_plan: leaf 2, no diagonal in lower[P], 64 levels,
+    tail search) on the panel graphs of tests/posegraph_topology_cases.py: a panel is four active free vertices in array
+    order.  Every method's plan is the boolean elimination's; method 0's tile count and chain are what
+    lba_posegraph_plan_info reports for the graph."""
+    import posegraph_oracle as po
+    import posegraph_topology_cases as tc
+    from amc_lba.posegraph import posegraph_plan_info
+    v, e, _ = tc.case(name)
+    ea, slot = po.activity(v, e)
+    s0, s1 = slot[e["v0"][ea]], slot[e["v1"][ea]]
+    both = (s0 >= 0) & (s1 >= 0)
+    P, Q = s0[both] // 4, s1[both] // 4
+    pr = sorted({(int(max(a, b)), int(min(a, b))) for a, b in zip(P, Q) if a != b})
+    info = posegraph_plan_info(v, e)
+    NP = info["panels"]
+    assert NP == (int((slot >= 0).sum()) + 3) // 4 and pr
+    for method in (0, 1, 2):
+        pl = plan_leaf(plan_harness, NP, pr, 2, False, method)
+        check_plan(NP, pr, pl)
+        if method == 0:
+            assert (pl["ntile"], pl["chain"]) == (info["tiles"], info["chain"])
+
+
 def test_random_sparse(plan_harness):
     rng = np.random.default_rng(3)
     for NP in (40, 120):
